@@ -6,7 +6,31 @@ by ``torch.distributed.run`` (one rank per GPU, RCCL) or, when started directly 
 (simclr_amd/runtime/launcher.py, the analogue of /root/reference/launch.py:202-259) before the
 parent touches the GPU.  Every rank asserts ``WORLD_SIZE == --gpus``.  W untimed steps, then
 exactly K timed steps bracketed by barrier + device synchronise, max over ranks, rank 0 prints
-ONE JSON line.
+ONE JSON line.  A plain run does only that (set-up, the execution-mode probe, warm-up, the K
+steps); ``--full`` adds the secondary measurements (the host issue cost on an idle device, the
+stale-pin check below).  ``config.final_loss`` is the loss of the last timed step (before
+``--full`` existed it was the loss three steps later, after the idle-device steps: the
+``BENCH_r0x.json`` records hold that later value).
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float32):
+the loss, the updated fp32 parameters (a fixed seeded sample of them) and the BatchNorm buffers;
+data, initial weights and augmentation are seeded and the kernels' reductions are atomic-free, so
+with the tile variants pinned (``--tiles pinned``, the default: the choices an autotuned run made
+on an MI355X, bench/tiles_mi355x.json) two runs write bitwise the same arrays and two builds can
+be compared array by array.  ``--tiles tune`` times every shape's candidates at the first step
+instead (near-ties then resolve differently from run to run, and with them the fp32 summation
+orders); with ``--save-tiles FILE`` it records a new table.  The execution-mode probe stays
+timing-driven and may pick another mode in another run: the comparison relies on eager issue,
+``hipGraphLaunch`` and the multi-stream replay computing bitwise the same, which
+tests/test_gpu_graph_exec.py (``test_stream_replay_matches_graph_replay``) and
+tests/test_gpu_forced_comm.py check.
+
+The pinned table is a recording, not a tuner: after a kernel change that adds a faster variant
+for a shape the headline does not move until the table is recorded again on an MI355X
+(``python bench.py --tiles tune --save-tiles bench/tiles_mi355x.json``; training never loads
+it).  ``--full`` times every shape afresh in one extra eager step and reports
+``config.tile_pins_retimed`` (shapes whose timed choice differs from the pin; about 5 of 80 flip
+between two runs of one build), and tests/test_bench_contract.py fails when a pin is no longer
+admissible or a shape has none.
 
 Config (BASELINE.json "ResNet-50 SimCLR CIFAR-10 bf16, batch=512 on 1 MI355X"): ResNet-50 with
 the CIFAR stem (3x3/s1, no maxpool — the north star's CIFAR-ResNet-50), 512 images per GPU (two
@@ -29,6 +53,7 @@ import sys
 import time
 from pathlib import Path
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -38,6 +63,8 @@ sys.path.insert(0, str(ROOT))
 METRIC = "pretrain images/sec (whole node) + CIFAR-10 linear-probe top-1, ResNet-50"
 PG_TIMEOUT_S = float(os.environ.get("SIMCLR_BENCH_PG_TIMEOUT", "300"))
 PROBE_ROUNDS = 3  # execution-mode probe: 3 x (2 eager + 2 graph) interleaved steps
+TILES = ROOT / "bench" / "tiles_mi355x.json"  # --tiles pinned (written by --save-tiles)
+DUMP_PARAMS = 1 << 22  # --dump-outputs: parameters written (16 MB of fp32), sampled above that
 
 
 def _free_port() -> int:
@@ -105,6 +132,25 @@ def _sync(dev, world):
         torch.cuda.synchronize(dev)
 
 
+def dump_outputs(path, loss, params, buffers) -> None:
+    """``--dump-outputs``: the state one step leaves behind, as float32 ``.npy`` files.  ``params``
+    is the flat fp32 parameter vector; above DUMP_PARAMS elements a fixed (seed 0) sample of it
+    is written, the same indices in every run and every build."""
+    d = Path(path)
+    d.mkdir(parents=True, exist_ok=True)
+    params = params.detach().reshape(-1)
+    if params.numel() > DUMP_PARAMS:
+        g = torch.Generator()
+        g.manual_seed(0)
+        idx = torch.randint(0, params.numel(), (DUMP_PARAMS,), generator=g)
+        params = params[idx.to(params.device)]
+    bufs = [b.detach().reshape(-1).float() for b in buffers if b.is_floating_point()]
+    arrays = {"loss": loss.detach().reshape(1), "params": params,
+              "buffers": torch.cat(bufs) if bufs else torch.zeros(0)}
+    for name, t in arrays.items():
+        np.save(d / f"{name}.npy", t.float().cpu().numpy())
+
+
 def _set_mode(tr, graph, mode: str) -> None:
     """eager | graph (hipGraphLaunch) | streams (native multi-stream replay of the graph)."""
     tr.graph = None if mode == "eager" else graph
@@ -143,6 +189,16 @@ def run_ours(args, rank, world, dev):
           f"runtime.bucket_mb={args.bucket_mb}"]
     cfg = task_config(compose(str(CONF_DIR), "config", ov, job_name="bench"))
     seed_everything(cfg["parameter"]["seed"])
+    from simclr_amd.ops import tuning
+    if args.tiles == "pinned":
+        # the tile variants an autotuned run selected on an MI355X, recorded (TILES): timed
+        # choices flip in near-ties from run to run and change the fp32 summation orders, so
+        # only a run on pinned tiles is bitwise repeatable.  A shape without a pin is tuned.
+        if TILES.exists():
+            tuning.load_pinned(TILES)
+        else:
+            print(f"[bench] {TILES} is missing: tile variants are tuned", file=sys.stderr,
+                  flush=True)
     # CIFAR-10's training-set length at every N: at N = 8 an epoch is 12 steps, as
     # in the reference; each rank's shard order is uploaded without a stream sync at rollover
     # (ImageNet-shape runs keep a smaller set: 50,000 224² images would be 7.5 GB of host RAM)
@@ -297,16 +353,20 @@ def run_ours(args, rank, world, dev):
         t1 = time.perf_counter()
         # host time spent issuing the steps (≈ wall time means the run is launch/CPU bound; with
         # a replay the host also blocks whenever the device queue is full)
-        args.host_issue_ms = host / args.steps * 1000.0
-        # the issue cost itself: steps issued onto an idle device (untimed, after the K steps)
-        idle = []
-        for _ in range(3):
+        args.host_issue_ms = host / max(1, args.steps) * 1000.0
+        args.final_loss = float(loss.item()) if loss is not None else float("nan")
+        if args.dump_outputs and rank == 0 and loss is not None:
+            dump_outputs(args.dump_outputs, loss, tr.store.master, tr.model.buffers())
+        if args.full:
+            # the issue cost itself: steps issued onto an idle device (untimed, after the K steps)
+            idle = []
+            for _ in range(3):
+                _sync(dev, world)
+                h0 = time.perf_counter()
+                loss = tr.step(next_batch())
+                idle.append(time.perf_counter() - h0)
             _sync(dev, world)
-            h0 = time.perf_counter()
-            loss = tr.step(next_batch())
-            idle.append(time.perf_counter() - h0)
-        _sync(dev, world)
-        args.host_issue_idle_ms = min(idle) * 1000.0
+            args.host_issue_idle_ms = min(idle) * 1000.0
         return t0, t1
 
     t0, t1 = measure()
@@ -329,7 +389,25 @@ def run_ours(args, rank, world, dev):
     args.exec_used = _exec_mode(tr)
     if tr.sreplay is not None:
         args.sreplay_stats = tr.sreplay.stats()
-    return t1 - t0, float(loss.item()) if loss is not None else float("nan")
+    used = tuning.pinned_used()
+    args.tile_variants = {"pinned": used, "unpinned": len(tuning.table()) - used}
+    if args.save_tiles and rank == 0:
+        tuning.save_table(args.save_tiles)
+    if args.full and tr.hip and used:
+        # stale-pin check (untimed, after everything else): one eager step with the pins dropped
+        # times every shape's candidates afresh.  Near-ties flip (about 5 of 80 shapes between
+        # two runs of one build); many more differing shapes mean the kernels have moved on and
+        # the table should be recorded again (--tiles tune --save-tiles)
+        before = tuning.table()
+        tuning.unpin()
+        g, tr.graph = tr.graph, None
+        tr.step(next_batch())
+        _sync(dev, world)
+        tr.graph = g
+        now = tuning.table()
+        args.tile_pins_retimed = {"shapes": len(before),
+                                  "differ": sum(1 for k, v in before.items() if now.get(k) != v)}
+    return t1 - t0, args.final_loss
 
 
 def run_reference(args, rank, world, dev):
@@ -363,7 +441,11 @@ def run_reference(args, rank, world, dev):
     for _ in range(args.steps):
         loss = step()
     _sync(dev, world)
-    return time.perf_counter() - t0, float(loss.item())
+    dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0 and loss is not None:
+        dump_outputs(args.dump_outputs, loss,
+                     torch.nn.utils.parameters_to_vector(model.parameters()), model.buffers())
+    return dt, float(loss.item()) if loss is not None else float("nan")
 
 
 def _stem_key(args) -> str:
@@ -409,6 +491,20 @@ def main(argv=None):
                          "replay, keep the fastest), or one of them forced")
     ap.add_argument("--bucket-mb", dest="bucket_mb", type=float, default=32.0)
     ap.add_argument("--impl", choices=["ours", "reference"], default="ours")
+    ap.add_argument("--tiles", choices=["pinned", "tune"], default="pinned",
+                    help="pinned: the recorded tile variants of bench/tiles_mi355x.json (bitwise "
+                         "repeatable runs; shapes it lacks are tuned); tune: time every shape's "
+                         "candidates at the first step")
+    ap.add_argument("--save-tiles", dest="save_tiles", metavar="FILE", default=None,
+                    help="write the tile variants this run used (with --tiles tune: a new "
+                         "bench/tiles_mi355x.json)")
+    ap.add_argument("--full", action="store_true",
+                    help="also take the secondary measurements (host issue cost of a step on an "
+                         "idle device, stale-pin check of the tile table); a plain run times "
+                         "the K steps and nothing else")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, parameters, BatchNorm "
+                         "buffers) as DIR/<name>.npy, float32")
     argv = list(sys.argv[1:] if argv is None else argv)
     args = ap.parse_args(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -439,7 +535,7 @@ def main(argv=None):
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
-    ms = dt / args.steps * 1000.0
+    ms = dt / max(1, args.steps) * 1000.0
     value = args.steps * args.batch * world / dt
     base = None
     bpath = ROOT / "profiles" / "reference_baseline.json"
@@ -492,6 +588,8 @@ def main(argv=None):
             "exec_mode_probe_ms": getattr(args, "mode_probe", None),
             "exec_mode": getattr(args, "exec_used", None),
             "stream_replay": getattr(args, "sreplay_stats", None),
+            "tile_variants": getattr(args, "tile_variants", None),
+            "tile_pins_retimed": getattr(args, "tile_pins_retimed", None),
             "bn_stats_comm": args.bn_comm,
             "bn_comm_probe_ms_ipc_rccl": getattr(args, "comm_probe_ms", None),
             "host_issue_ms_per_step": (round(args.host_issue_ms, 3)

@@ -5,6 +5,13 @@ with HIP events on an otherwise idle device (3 launches after 1 warm-up, best of
 ``SIMCLR_AUTOTUNE_ROUNDS`` = 2 sweeps) and the fastest is cached for the process; inside a
 hipGraph capture, or with ``SIMCLR_AUTOTUNE=0``, the cached (else default) variant is used.
 Tuning launches write only to scratch outputs, so it has no side effects.
+
+bench.py alone pins its shapes to a recorded table (``pin`` / ``load_pinned``,
+bench/tiles_mi355x.json) so that its runs are bitwise repeatable.  After adding, renumbering or
+speeding up a tile variant, record that table again on an MI355X
+(``python bench.py --tiles tune --save-tiles bench/tiles_mi355x.json``): until then the headline
+keeps running the old choices (``bench.py --full`` reports how many pins a fresh tuning would
+change).
 """
 from __future__ import annotations
 
@@ -14,6 +21,7 @@ from typing import Callable, Dict, Hashable, Sequence
 import torch
 
 _CACHE: Dict[Hashable, int] = {}
+_PINNED: Dict[Hashable, int] = {}
 ENABLED = os.environ.get("SIMCLR_AUTOTUNE", "1") != "0"
 ROUNDS = int(os.environ.get("SIMCLR_AUTOTUNE_ROUNDS", "2"))
 
@@ -38,6 +46,10 @@ def pick(key: Hashable, candidates: Sequence[int], default: int,
     cands = list(candidates)
     if not cands:
         return default
+    if ENABLED and _PINNED.get(key) in cands:
+        # a recorded choice (pin): taken without trials, only while it is still admissible
+        _CACHE[key] = _PINNED[key]
+        return _CACHE[key]
     if (not ENABLED or len(cands) == 1 or not torch.cuda.is_available()
             or torch.cuda.is_current_stream_capturing()):
         choice = default if default in cands else cands[0]
@@ -69,6 +81,46 @@ def pick(key: Hashable, candidates: Sequence[int], default: int,
 
 def table() -> Dict[Hashable, int]:
     return dict(_CACHE)
+
+
+def _tuple(x):
+    return tuple(_tuple(v) for v in x) if isinstance(x, (list, tuple)) else x
+
+
+def pin(choices: Dict[Hashable, int]) -> None:
+    """Recorded choices that ``pick`` takes instead of timing the candidates (a shape without a
+    pin, or whose pinned variant is no longer admissible, is tuned as usual).  Timed choices
+    differ in near-ties from run to run, and with them the fp32 summation orders; pinned ones
+    make a run bitwise repeatable at the tuned speed (bench.py)."""
+    _PINNED.update({_tuple(k): int(v) for k, v in choices.items()})
+
+
+def unpin() -> None:
+    """Drop the pins and the choices made so far: every shape is tuned at its next eager launch."""
+    _PINNED.clear()
+    _CACHE.clear()
+
+
+def pinned_used() -> int:
+    """How many of the choices in use came from a pin."""
+    return sum(1 for k, v in _CACHE.items() if _PINNED.get(k) == v)
+
+
+def save_table(path) -> int:
+    """Write the choices in use as JSON (``load_pinned`` reads it back)."""
+    import json
+    rows = sorted(([list(k), v] for k, v in _CACHE.items()), key=repr)
+    with open(path, "w") as f:
+        f.write("[\n" + ",\n".join(json.dumps(r) for r in rows) + "\n]\n")
+    return len(rows)
+
+
+def load_pinned(path) -> int:
+    import json
+    with open(path) as f:
+        rows = json.load(f)
+    pin({_tuple(k): v for k, v in rows})
+    return len(rows)
 
 
 def sync_from_rank0(group=None) -> int:

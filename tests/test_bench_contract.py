@@ -36,6 +36,85 @@ def test_bench_gpus2_self_launches_two_ranks(tmp_path):
     assert j["value"] > 0 and j["dtype"] == "fp32"
 
 
+def _bench_one_rank(tmp_path, out, *extra):
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--model", "resnet18",
+           "--batch", "8", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out), *extra]
+    r = subprocess.run(cmd, cwd=str(tmp_path), env=_env(), capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    return json.loads(lines[0])
+
+
+def test_bench_dump_outputs_and_full(tmp_path):
+    """``--dump-outputs`` writes the last timed step's loss / parameters / BatchNorm buffers as
+    float32 .npy (64 MB at most), the same arrays from run to run; the idle-device issue cost is
+    measured only with ``--full``, after the dump, so it does not change what is written."""
+    import numpy as np
+    plain = _bench_one_rank(tmp_path, tmp_path / "a")
+    full = _bench_one_rank(tmp_path, tmp_path / "b", "--full")
+    for j in (plain, full):
+        assert j["steps"] == 2 and j["warmup"] == 1 and j["ms_per_step"] > 0
+        assert j["value"] == pytest.approx(8 * 1000.0 / j["ms_per_step"], rel=1e-3)
+        assert {"metric", "unit", "higher_is_better", "dtype"} <= set(j)
+    assert plain["config"]["host_issue_ms_idle_device"] is None
+    assert full["config"]["host_issue_ms_idle_device"] > 0
+    names = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert names == ["buffers.npy", "loss.npy", "params.npy"]
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), n
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == pytest.approx(
+        plain["config"]["final_loss"], rel=1e-6)
+
+
+@pytest.mark.gpu
+def test_bench_flagship_runs_on_pinned_tiles(tmp_path):
+    """The flagship configuration times nothing at its first step: every shape takes its recorded
+    tile variant (bench/tiles_mi355x.json), so two runs compute bitwise the same.  A kernel change
+    that makes a pin inadmissible, or adds a shape, shows here as a tuned entry: record the table
+    again (``bench.py --tiles tune --save-tiles bench/tiles_mi355x.json``)."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SIMCLR_AUTOTUNE"):
+        env.pop(k, None)
+    # the default path: capture, planning replay, execution-mode probe (timing-driven; whichever
+    # mode it keeps, the three compute bitwise the same: test_gpu_graph_exec / _forced_comm)
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "0"]
+    r = subprocess.run(cmd, cwd=str(tmp_path), env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["config"]["exec_mode"] in ("eager", "graph", "streams")
+    assert j["config"]["exec_mode_probe_ms"] is not None
+    assert j["config"]["tile_variants"]["unpinned"] == 0, j["config"]["tile_variants"]
+    assert j["config"]["tile_variants"]["pinned"] > 0
+    assert j["config"]["tile_pins_retimed"] is None  # the stale-pin check belongs to --full
+
+
+def test_dump_outputs_samples_large_parameter_vectors(tmp_path):
+    import importlib.util
+    import numpy as np
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_script", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    n = bench.DUMP_PARAMS + 12345
+    params = torch.arange(n, dtype=torch.float32)
+    bufs = [torch.ones(3), torch.zeros(2, dtype=torch.long), torch.full((2,), 2.0)]
+    for d in ("a", "b"):
+        bench.dump_outputs(tmp_path / d, torch.tensor(1.5), params, bufs)
+    a, b = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "b" / "params.npy")
+    assert a.shape == (bench.DUMP_PARAMS,) and a.dtype == np.float32 and np.array_equal(a, b)
+    assert 0 <= a.min() and a.max() < n and len(np.unique(a)) > bench.DUMP_PARAMS // 2
+    assert np.load(tmp_path / "a" / "buffers.npy").tolist() == [1.0, 1.0, 1.0, 2.0, 2.0]
+    assert np.load(tmp_path / "a" / "loss.npy").tolist() == [1.5]
+
+
 def test_bench_world_mismatch_is_an_error(tmp_path):
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
