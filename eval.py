@@ -1,6 +1,7 @@
 """Downstream evaluation entry point (reference: /root/reference/eval.py).
 
-    python eval.py experiment.target_dir=PATH [parameter.classifier={centroid,linear,nonlinear}]
+    python eval.py experiment.target_dir=PATH [parameter.classifier={centroid,knn,linear,nonlinear}]
+                   [parameter.knn_k=200] [parameter.knn_t=0.1]
                    [parameter.use_full_encoder=true]
 """
 from simclr_amd.config import hydra_main

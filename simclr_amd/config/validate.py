@@ -32,6 +32,10 @@ def check_eval_conf(cfg) -> None:
     _check(e["base_cnn"] in {"resnet18", "resnet50"}, "experiment.base_cnn must be resnet18/50")
     _check(e["lr"] > 0.0, "experiment.lr must be > 0")
     _check(e["decay"] >= 0.0, "experiment.decay must be >= 0")
+    if p.get("classifier") == "knn":
+        k, t = p.get("knn_k"), p.get("knn_t")
+        _check(k is None or k >= 1, "parameter.knn_k must be >= 1")
+        _check(t is None or t > 0.0, "parameter.knn_t must be > 0")
 
 
 def check_save_features_conf(cfg) -> None:

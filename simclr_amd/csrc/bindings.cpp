@@ -1059,10 +1059,84 @@ void class_sums_op(const Tensor& X, const Tensor& y, int64_t NC, const Tensor& s
              pcnt.data_ptr<float>(), f32w(sums, "sums"), f32w(counts, "counts"), cur_stream());
 }
 
+// ------------------------------------------------------------------------------- k-NN probe
+void knn_normalize_op(const Tensor& x, const Tensor& out) {
+  TORCH_CHECK(x.dim() == 2 && out.dim() == 2, "knn_normalize: x [R][D], out [R][Dp]");
+  TORCH_CHECK(x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16,
+              "knn_normalize: x must be fp32 or bf16, got ", x.scalar_type());
+  check_dev(x, x.scalar_type(), "x");
+  const int64_t R = x.size(0), D = x.size(1), Dp = out.size(1);
+  const int64_t ks = knn_kstep();
+  TORCH_CHECK(R >= 1 && R < (1ll << 31) && D >= 1, "knn_normalize: empty input");
+  TORCH_CHECK(out.size(0) == R && Dp == (D + ks - 1) / ks * ks && Dp <= 4096,
+              "knn_normalize: out must be [R][D rounded up to ", ks, "] with Dp <= 4096, got [",
+              out.size(0), "][", Dp, "] for D ", D);
+  knn_normalize(x.data_ptr(), x.scalar_type() == at::kBFloat16, (int)R, (int)D, (int)Dp,
+                bfw(out, "out"), cur_stream());
+}
+
+void knn_topk_op(const Tensor& qn, const Tensor& bn, int64_t k, bool exclude_self,
+                 int64_t self_offset, const Tensor& vals, const Tensor& idx) {
+  TORCH_CHECK(qn.dim() == 2 && bn.dim() == 2, "knn_topk: qn [Q][Dp], bn [N][Dp]");
+  const int64_t Q = qn.size(0), N = bn.size(0), Dp = qn.size(1);
+  TORCH_CHECK(bn.size(1) == Dp, "knn_topk: query and bank widths differ");
+  TORCH_CHECK(Dp >= knn_kstep() && Dp % knn_kstep() == 0 && Dp <= 4096,
+              "knn_topk: Dp must be a multiple of ", knn_kstep(), " and <= 4096, got ", Dp);
+  TORCH_CHECK(Q >= 1 && N >= 1 && Q <= (1ll << 31) - 256 && N <= (1ll << 31) - 256,
+              "knn_topk: Q and N must be in [1, 2^31 - 256]");
+  TORCH_CHECK(k >= 1 && k <= knn_max_k(), "knn_topk: k must be in [1, ", knn_max_k(), "], got ", k);
+  TORCH_CHECK(k <= N - (exclude_self ? 1 : 0), "knn_topk: k exceeds the selectable bank rows");
+  TORCH_CHECK(self_offset > -(1ll << 40) && self_offset < (1ll << 40), "knn_topk: self_offset");
+  TORCH_CHECK(knn_topk_lds() <= 160 * 1024, "knn_topk: LDS budget");
+  TORCH_CHECK(vals.dim() == 2 && vals.size(0) == Q && vals.size(1) == k, "knn_topk: vals [Q][k]");
+  TORCH_CHECK(idx.dim() == 2 && idx.size(0) == Q && idx.size(1) == k, "knn_topk: idx [Q][k]");
+  check_dev(idx, at::kInt, "idx");
+  const auto o = qn.options().dtype(at::kLong);
+  at::Tensor buf = at::empty({(int64_t)knn_buf_keys((int)Q, (int)N)}, o);
+  at::Tensor cand = at::empty({(int64_t)knn_cand_keys((int)Q, (int)N, (int)k)}, o);
+  knn_topk(bf(qn, "qn"), bf(bn, "bn"), (int)Q, (int)N, (int)Dp, (int)k, exclude_self,
+           (long long)self_offset, reinterpret_cast<unsigned long long*>(buf.data_ptr()),
+           reinterpret_cast<unsigned long long*>(cand.data_ptr()), f32w(vals, "vals"),
+           idx.data_ptr<int>(), cur_stream());
+}
+
+int64_t knn_scratch_bytes_op(int64_t Q, int64_t N, int64_t k) {
+  TORCH_CHECK(Q >= 1 && N >= 1 && k >= 1 && Q < (1ll << 31) && N < (1ll << 31), "knn_scratch_bytes");
+  return (int64_t)(8 * (knn_buf_keys((int)Q, (int)N) + knn_cand_keys((int)Q, (int)N, (int)k)));
+}
+
+void knn_vote_op(const Tensor& vals, const Tensor& idx, const Tensor& labels, int64_t C,
+                 double temperature, const Tensor& targets, const Tensor& scores,
+                 const Tensor& rank) {
+  TORCH_CHECK(vals.dim() == 2 && idx.dim() == 2 && vals.sizes() == idx.sizes(),
+              "knn_vote: vals and idx [Q][k]");
+  const int64_t Q = vals.size(0), k = vals.size(1), N = labels.numel();
+  TORCH_CHECK(Q >= 1 && Q < (1ll << 31) && N >= 1 && N < (1ll << 31), "knn_vote: Q, N");
+  TORCH_CHECK(k >= 1 && k <= knn_max_k(), "knn_vote: k must be in [1, ", knn_max_k(), "]");
+  TORCH_CHECK(C >= 1 && C <= knn_max_classes(), "knn_vote: num_classes must be in [1, ",
+              knn_max_classes(), "], got ", C);
+  TORCH_CHECK(temperature > 0.0, "knn_vote: temperature must be > 0");
+  check_dev(idx, at::kInt, "idx");
+  check_dev(labels, at::kLong, "labels");
+  check_dev(targets, at::kLong, "targets");
+  check_dev(rank, at::kInt, "rank");
+  TORCH_CHECK(targets.numel() == Q && rank.numel() == Q, "knn_vote: targets / rank [Q]");
+  TORCH_CHECK(scores.dim() == 2 && scores.size(0) == Q && scores.size(1) == C,
+              "knn_vote: scores [Q][C]");
+  knn_vote(f32(vals, "vals"), idx.data_ptr<int>(), labels.data_ptr<int64_t>(),
+           targets.data_ptr<int64_t>(), (int)Q, (int)k, (int)N, (int)C, (float)(1.0 / temperature),
+           f32w(scores, "scores"), rank.data_ptr<int>(), cur_stream());
+}
+
 }  // namespace
 
 
 TORCH_LIBRARY(simclr_amd, m) {
+  m.def("knn_normalize(Tensor x, Tensor(a!) out) -> ()", &knn_normalize_op);
+  m.def("knn_topk(Tensor qn, Tensor bn, int k, bool exclude_self, int self_offset, Tensor(a!) vals, Tensor(b!) idx) -> ()", &knn_topk_op);
+  m.def("knn_scratch_bytes(int Q, int N, int k) -> int", &knn_scratch_bytes_op);
+  m.def("knn_kstep() -> int", []() -> int64_t { return knn_kstep(); });
+  m.def("knn_vote(Tensor vals, Tensor idx, Tensor labels, int C, float temperature, Tensor targets, Tensor(a!) scores, Tensor(b!) rank) -> ()", &knn_vote_op);
   m.def("maxpool_fwd(Tensor x, Tensor(a!) y, Tensor(b!) arg, int K, int S, int P) -> ()", &maxpool_fwd_op);
   m.def("maxpool_bwd(Tensor dy, Tensor arg, Tensor(a!) dx, int K, int S, int P) -> ()", &maxpool_bwd_op);
   m.def("stem_s2d(Tensor img, int creal, int P, Tensor(a!) xs) -> ()", &stem_s2d_op);

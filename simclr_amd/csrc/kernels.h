@@ -259,3 +259,19 @@ int class_sums_groups(int N);
 void class_sums(const float* X, const int64_t* y, int N, int D, int NC, float* part, float* pcnt,
                 float* sums, float* counts, hipStream_t s);
 
+
+// ---- knn.hip: weighted k-NN probe (normalise + round, fused similarity / top-k, class vote)
+int knn_kstep();        // Dp is D rounded up to this
+int knn_max_k();
+int knn_max_classes();
+size_t knn_topk_lds();  // bytes of LDS of the top-k kernel
+int knn_splits(int Q, int N);
+size_t knn_buf_keys(int Q, int N);          // 8-byte keys of append-buffer scratch
+size_t knn_cand_keys(int Q, int N, int k);  // 8-byte keys of per-split candidates
+void knn_normalize(const void* x, bool x_is_bf16, int R, int D, int Dp, uint16_t* out,
+                   hipStream_t s);
+void knn_topk(const uint16_t* Qn, const uint16_t* Bn, int Q, int N, int Dp, int k, bool has_self,
+              long long self_off, unsigned long long* buf, unsigned long long* cand, float* vals,
+              int* idx, hipStream_t s);
+void knn_vote(const float* vals, const int* idx, const int64_t* labels, const int64_t* targets,
+              int Q, int k, int N, int C, float inv_t, float* scores, int* rank, hipStream_t s);

@@ -1,9 +1,12 @@
-"""Downstream probes on frozen features: centroid, linear and nonlinear classifiers.
+"""Downstream probes on frozen features: centroid, weighted k-NN, linear and nonlinear classifiers.
 
 Parity: ``centroid_eval`` (``/root/reference/eval.py:61-85``), ``learnable_eval``
 (eval.py:88-190) and the results-dict schema of eval.py:279-319:
 
 * centroid: class-mean weights (unnormalised) · dot-product scores, top-1 / top-k accuracy;
+* knn: the weighted k-nearest-neighbour classifier of Wu et al. (InstDisc), not in the reference:
+  cosine neighbours in the train features, votes ``exp((sim - 1) / T)``; the train numbers are
+  leave-one-out (``ops/knn.py`` holds the contract);
 * linear / nonlinear: SGD(lr = lr·batches/256, momentum, **nesterov=True**, wd = decay),
   ``CosineAnnealingLR(T_max = epochs·ceil(N/batches))`` stepped every batch, shuffled batches;
   after every epoch train and val (top-1, top-k, mean CE) are recomputed; the JSON reports the
@@ -25,6 +28,8 @@ import torch.nn.functional as F
 
 from ..models.heads import CentroidClassifier, LinearClassifier, NonLinearClassifier
 from ..ops.classify import ce_rank, cross_entropy
+from ..ops.knn import knn_topk, knn_vote
+from ..utils.misc import cfg_get
 from ..optim.schedule import cosine_lr
 
 log = logging.getLogger(__name__)
@@ -67,6 +72,23 @@ def centroid_eval(ds: DownstreamDataset, classifier: CentroidClassifier, top_k: 
                   batch_size: int = 4096) -> Tuple[float, float]:
     _, c1, ck = _eval_counts(classifier, ds, top_k, batch_size, with_loss=False)
     return c1, ck
+
+
+@torch.no_grad()
+def knn_eval(bank: DownstreamDataset, query: DownstreamDataset, num_classes: int, k: int = 200,
+             temperature: float = 0.1, top_k: int = 5, leave_one_out: bool = False,
+             return_scores: bool = False):
+    """(top-1, top-k) accuracy of the weighted k-NN vote of ``query`` against ``bank``.  With
+    ``leave_one_out`` the queries are the bank itself and a row is never its own neighbour."""
+    vals, idx = knn_topk(query.data, bank.data.to(query.data.device), k,
+                         self_offset=0 if leave_one_out else None)
+    scores, rank = knn_vote(vals, idx, bank.targets, num_classes, temperature, query.targets)
+    kk = max(1, min(top_k, num_classes))
+    n = max(1, len(query))
+    c = torch.stack([(rank == 0).sum(), (rank < kk).sum()]).cpu().tolist()
+    if return_scores:
+        return c[0] / n, c[1] / n, scores
+    return c[0] / n, c[1] / n
 
 
 def _eval_counts(classifier, ds: DownstreamDataset, top_k: int, batch_size: int,
@@ -158,13 +180,27 @@ def run_probe(cfg, kind: str, train: DownstreamDataset, val: DownstreamDataset, 
             "val_acc": val_acc,
             "val_top_{}_acc".format(top_k): val_topk,
         }
+    if kind == "knn":
+        k = int(cfg_get(cfg, "parameter.knn_k", 200))
+        t = float(cfg_get(cfg, "parameter.knn_t", 0.1))
+        train_acc, train_topk = knn_eval(train, train, num_classes, k, t, top_k, leave_one_out=True)
+        val_acc, val_topk = knn_eval(train, val, num_classes, k, t, top_k)
+        logging.info("train acc: {}, val acc: {}".format(train_acc, val_acc))
+        return {
+            "train_acc": train_acc,
+            "train_top_{}_acc".format(top_k): train_topk,
+            "val_acc": val_acc,
+            "val_top_{}_acc".format(top_k): val_topk,
+            "knn_k": k,
+            "knn_t": t,
+        }
     F_ = train.data.shape[1]
     if kind == "linear":
         clf = LinearClassifier(F_, num_classes).to(device)
     elif kind.replace("-", "") == "nonlinear":
         clf = NonLinearClassifier(F_, num_classes).to(device)
     else:
-        raise ValueError(f"unknown classifier {kind!r} (centroid | linear | nonlinear)")
+        raise ValueError(f"unknown classifier {kind!r} (centroid | knn | linear | nonlinear)")
     tr_acc, tr_topk, tr_loss, va_acc, va_topk, va_loss = learnable_eval(
         cfg, clf, train, val, top_k, seed=cfg["parameter"]["seed"])
     logging.info("train acc: {}, val acc: {}".format(max(tr_acc), max(va_acc)))
