@@ -9,8 +9,23 @@ def _check(cond: bool, msg: str) -> None:
         raise AssertionError(msg)
 
 
+def _check_blur(cfg) -> None:
+    """The opt-in ``data.blur_kernel``: 0 (derive from the output size) or odd within the
+    augmentation op's limits (``data.augment_ref.MAX_BLUR_KERNEL``)."""
+    from ..data.augment_ref import MAX_BLUR_KERNEL
+    data = cfg.get("data") if hasattr(cfg, "get") else None
+    ks = (data or {}).get("blur_kernel")
+    if ks is None:
+        return
+    _check(isinstance(ks, int) and not isinstance(ks, bool), "data.blur_kernel must be an integer")
+    _check(ks >= 0, "data.blur_kernel must be >= 0")
+    _check(ks == 0 or (ks % 2 == 1 and ks >= 3), "data.blur_kernel must be 0 or odd and >= 3")
+    _check(ks <= MAX_BLUR_KERNEL, f"data.blur_kernel must be <= {MAX_BLUR_KERNEL}")
+
+
 def check_pretrain_conf(cfg) -> None:
     p, e = cfg["parameter"], cfg["experiment"]
+    _check_blur(cfg)
     _check(p["temperature"] > 0.0, "parameter.temperature must be > 0")
     _check(p["epochs"] > 0, "parameter.epochs must be > 0")
     _check(e["batches"] > 0, "experiment.batches must be > 0")
@@ -46,6 +61,7 @@ def check_save_features_conf(cfg) -> None:
 
 def check_supervised_conf(cfg) -> None:
     p, e = cfg["parameter"], cfg["experiment"]
+    _check_blur(cfg)
     _check(p["epochs"] > 0, "parameter.epochs must be > 0")
     _check(e["batches"] > 0, "experiment.batches must be > 0")
     _check(1.0 > p["momentum"] >= 0, "parameter.momentum must be in [0, 1)")

@@ -9,6 +9,7 @@
 #include <c10/util/Exception.h>
 #include <torch/library.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "kernels.h"
@@ -904,8 +905,21 @@ void lr_step_op(const Tensor& step, const Tensor& lr, double lr0, int64_t warmup
 void augment_op(const Tensor& images, const c10::optional<Tensor>& indices, int64_t n,
                 int64_t views, int64_t OH, int64_t OW, int64_t Cpad, double strength, int64_t seed,
                 int64_t counter, int64_t view_offset, int64_t flags, const Tensor& out,
-                const c10::optional<Tensor>& params) {
+                const c10::optional<Tensor>& params, int64_t blur_kernel) {
   check_dev(images, at::kByte, "images");
+  TORCH_CHECK(n >= 0 && views >= 0 && OH > 0 && OW > 0, "augment: sizes");
+  if (blur_kernel != 0) {
+    // Gaussian blur (augment.hip): an odd kernel in [3, limit] whose half width reflect padding
+    // can serve, on augmented launches only, at a size whose bands fit the kernel's LDS
+    const int64_t lim = augment_max_blur_kernel();
+    TORCH_CHECK(blur_kernel >= 3 && blur_kernel % 2 == 1 && blur_kernel <= lim,
+                "augment: blur_kernel must be 0 (off) or odd in [3, ", lim, "], got ", blur_kernel);
+    TORCH_CHECK((blur_kernel - 1) / 2 <= std::min(OH, OW) - 1, "augment: blur_kernel ",
+                blur_kernel, " too large for reflect padding of a ", OH, "x", OW, " output");
+    TORCH_CHECK(flags & 1, "augment: blur_kernel needs the augmented mode (flags & 1)");
+    TORCH_CHECK(augment_blur_band((int)OH, (int)OW, (int)blur_kernel) > 0, "augment: a ", OH, "x",
+                OW, " output with blur_kernel ", blur_kernel, " does not fit the blur's LDS bands");
+  }
   TORCH_CHECK(images.dim() == 4 && images.size(3) == 3, "augment: images must be [N,H,W,3] uint8");
   const int H = images.size(1), W = images.size(2);
   TORCH_CHECK(Cpad >= 3, "augment: Cpad >= 3");
@@ -926,8 +940,10 @@ void augment_op(const Tensor& images, const c10::optional<Tensor>& indices, int6
   }
   simclr_augment(images.data_ptr<uint8_t>(), idx, n, views, H, W, OH, OW, Cpad, (float)strength,
                  (uint64_t)seed, (uint64_t)counter, view_offset, flags, bfw(out, "out"), po,
-                 cur_stream());
+                 (int)blur_kernel, cur_stream());
 }
+
+int64_t augment_max_blur_kernel_op() { return augment_max_blur_kernel(); }
 
 // ---- eval.hip: maxpool (K2), cross-entropy + top-k (K10), centroid class sums (K11)
 void maxpool_fwd_op(const Tensor& x, const Tensor& y, const Tensor& arg, int64_t K, int64_t S,
@@ -1213,5 +1229,6 @@ TORCH_LIBRARY(simclr_amd, m) {
   m.def("lars_norms(Tensor p, Tensor g, Tensor chunk_beg, Tensor chunk_end, float grad_scale, Tensor(a!) norms) -> ()", &lars_norms_op);
   m.def("lars_update(Tensor(a!) p, Tensor g, Tensor(b!) mom, Tensor(c!)? shadow, Tensor chunk_seg, Tensor chunk_beg, Tensor chunk_end, Tensor seg_chunk_beg, Tensor seg_chunk_end, Tensor seg_wd, Tensor seg_flags, Tensor norms, Tensor lr, float momentum, float trust, float eps, float grad_scale, bool nesterov) -> ()", &lars_update_op);
   m.def("lr_step(Tensor(a!) step, Tensor(b!) lr, float lr0, int warmup, int total, int mode) -> ()", &lr_step_op);
-  m.def("augment(Tensor images, Tensor? indices, int n, int views, int OH, int OW, int Cpad, float strength, int seed, int counter, int view_offset, int flags, Tensor(a!) out, Tensor(b!)? params) -> ()", &augment_op);
+  m.def("augment(Tensor images, Tensor? indices, int n, int views, int OH, int OW, int Cpad, float strength, int seed, int counter, int view_offset, int flags, Tensor(a!) out, Tensor(b!)? params, int blur_kernel=0) -> ()", &augment_op);
+  m.def("augment_max_blur_kernel() -> int", &augment_max_blur_kernel_op);
 }

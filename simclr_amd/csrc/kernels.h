@@ -236,7 +236,11 @@ void lr_schedule_step(int64_t* step, float* lr_out, double lr0, int64_t warmup, 
 // ---- augment.hip
 void simclr_augment(const uint8_t* images, const int64_t* indices, int n, int views, int H, int W,
                     int OH, int OW, int Cpad, float strength, uint64_t seed, uint64_t counter,
-                    int view_offset, int flags, uint16_t* out, float* params_out, hipStream_t s);
+                    int view_offset, int flags, uint16_t* out, float* params_out, int blur_kernel,
+                    hipStream_t s);
+int augment_max_blur_kernel();  // blur_kernel: 0 (off) or odd in [3, this]
+// output rows per LDS band of a blurred image; 0: (OH, OW, ks) cannot be blurred
+int augment_blur_band(int OH, int OW, int ks);
 
 // ---- eval.hip: maxpool (K2), cross-entropy + top-k (K10), centroid class sums (K11)
 void maxpool_fwd(const uint16_t* x, uint16_t* y, uint8_t* arg, int Nb, int H, int W, int C,

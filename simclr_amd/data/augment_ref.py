@@ -13,6 +13,7 @@ from typing import Optional, Tuple
 import numpy as np
 
 M64 = (1 << 64) - 1
+MAX_BLUR_KERNEL = 33  # the op's upper limit of blur_kernel (csrc/augment.hip AUG_MAX_BLUR_KS)
 
 
 def splitmix64(x: int) -> int:
@@ -45,7 +46,7 @@ def image_key(seed: int, counter: int, view: int, idx: int) -> int:
     return splitmix64((seed ^ a ^ b) & M64)
 
 
-def sample_params(rng: Rng, H: int, W: int, strength: float) -> dict:
+def sample_params(rng: Rng, H: int, W: int, strength: float, blur: bool = False) -> dict:
     f32 = np.float32
     area = f32(H * W)
     lr0, lr1 = f32(math.log(3 / 4)), f32(math.log(4 / 3))
@@ -87,6 +88,11 @@ def sample_params(rng: Rng, H: int, W: int, strength: float) -> dict:
     P["fs"] = rng.uniform(max(0.0, 1 - s), 1 + s)
     P["fh"] = rng.uniform(-hh, hh)
     P["gray"] = rng.uniform() < 0.2
+    if blur:  # RandomApply([GaussianBlur], p=0.5): the last two draws, made only when enabled
+        P["blur"] = not (0.5 < rng.uniform())
+        P["sigma"] = rng.uniform(0.1, 2.0)
+    else:
+        P["blur"], P["sigma"] = False, 0.0
     return P
 
 
@@ -123,7 +129,60 @@ def _hsv2rgb(h, s, v):
     return r, g, b
 
 
-def apply_params(img: np.ndarray, P: dict, OH: int, OW: int) -> np.ndarray:
+def default_blur_kernel(out_size: int) -> int:
+    """SimCLR's kernel of about 10 % of the side, made odd: 3 at 32, 7 at 64, 23 at 224."""
+    return 2 * int(math.floor(0.05 * out_size)) + 1
+
+
+def check_blur_kernel(ks: int, OH: int, OW: int) -> None:
+    """The limits of the op (``csrc/bindings.cpp``); 0 means off."""
+    if ks == 0:
+        return
+    if ks < 3 or ks % 2 == 0 or ks > MAX_BLUR_KERNEL:
+        raise ValueError(f"blur_kernel must be 0 or odd in [3, {MAX_BLUR_KERNEL}], got {ks}")
+    if (ks - 1) // 2 > min(OH, OW) - 1:
+        raise ValueError(f"blur_kernel {ks} too large for reflect padding of a {OH}x{OW} output")
+
+
+def blur_weights(ks: int, sigma: float) -> np.ndarray:
+    """fp32 taps exp(-0.5 (x / sigma)^2), x = i - (ks-1)/2, over their sequential fp32 sum."""
+    f32 = np.float32
+    q = (np.arange(ks, dtype=f32) - f32((ks - 1) // 2)) / f32(sigma)
+    e = np.exp(f32(-0.5) * q * q).astype(f32)
+    s = f32(0.0)
+    for v in e:
+        s = f32(s + v)
+    return (e / s).astype(f32)
+
+
+def _reflect(i: np.ndarray, n: int) -> np.ndarray:
+    i = np.where(i < 0, -i, i)
+    return np.where(i >= n, 2 * (n - 1) - i, i)
+
+
+def gaussian_blur(pix: np.ndarray, ks: int, sigma: float) -> np.ndarray:
+    """torchvision's ``gaussian_blur`` of a uint8 image as the kernel computes it: pix [H, W] or
+    [H, W, C] with integer values 0..255 -> float32 of the same shape.  Separable (horizontal,
+    then vertical, taps accumulated in index order, the intermediate kept in fp32), reflect
+    padding without edge repeat, clip(floor(v + 0.5), 0, 255) at the end."""
+    f32 = np.float32
+    H, W = pix.shape[0], pix.shape[1]
+    r = (ks - 1) // 2
+    if ks < 3 or ks % 2 == 0 or r > min(H, W) - 1:
+        raise ValueError(f"gaussian_blur: bad kernel size {ks} for a {H}x{W} image")
+    w = blur_weights(ks, sigma)
+    src = pix.astype(f32)
+    xs, ys = np.arange(W), np.arange(H)
+    hor = np.zeros_like(src)
+    for t in range(ks):
+        hor = (hor + w[t] * src[:, _reflect(xs + (t - r), W)]).astype(f32)
+    out = np.zeros_like(src)
+    for t in range(ks):
+        out = (out + w[t] * hor[_reflect(ys + (t - r), H)]).astype(f32)
+    return np.clip(np.floor(out + f32(0.5)), 0, 255).astype(f32)
+
+
+def apply_params(img: np.ndarray, P: dict, OH: int, OW: int, blur_kernel: int = 0) -> np.ndarray:
     """img uint8 [H, W, 3] -> float32 [OH, OW, 3] in [0, 255] (before /255)."""
     f32 = np.float32
     ch, cw, ci, cj = P["ch"], P["cw"], P["ci"], P["cj"]
@@ -173,13 +232,19 @@ def apply_params(img: np.ndarray, P: dict, OH: int, OW: int) -> np.ndarray:
     if P["gray"]:
         l = _luma(R, G, B).astype(f32)
         R = G = B = l
-    return np.stack([R, G, B], axis=-1).astype(f32)
+    out = np.stack([R, G, B], axis=-1).astype(f32)
+    if blur_kernel and P.get("blur", False):
+        out = gaussian_blur(out, blur_kernel, P["sigma"])
+    return out
 
 
 def augment_batch(images: np.ndarray, indices: np.ndarray, views: int, OH: int, OW: int,
                   strength: float, seed: int, counter: int, view_offset: int = 0,
-                  augment: bool = True) -> np.ndarray:
+                  augment: bool = True, blur_kernel: int = 0) -> np.ndarray:
     """-> float32 [views * n, 3, OH, OW] in [0, 1] (view-major, like the kernel)."""
+    check_blur_kernel(blur_kernel, OH, OW)
+    if blur_kernel and not augment:
+        raise ValueError("blur_kernel needs augment=True")
     n = len(indices)
     H, W = images.shape[1], images.shape[2]
     out = np.empty((views * n, 3, OH, OW), dtype=np.float32)
@@ -188,8 +253,8 @@ def augment_batch(images: np.ndarray, indices: np.ndarray, views: int, OH: int, 
             img = images[int(idx)]
             if augment:
                 P = sample_params(Rng(image_key(seed, counter, v + view_offset, int(idx))), H, W,
-                                  strength)
-                pix = apply_params(img, P, OH, OW)
+                                  strength, blur=blur_kernel != 0)
+                pix = apply_params(img, P, OH, OW, blur_kernel)
             else:
                 pix = img.astype(np.float32)
             out[v * n + b] = pix.transpose(2, 0, 1) / 255.0

@@ -19,6 +19,7 @@ from typing import Iterator, List, Optional, Tuple
 import numpy as np
 import torch
 
+from ..utils.misc import cfg_get
 from . import augment_ref
 from .datasets import ImageDataset
 
@@ -53,6 +54,17 @@ def shard_indices(n: int, epoch: int, rank: int, world: int, shuffle: bool = Tru
     return shard_indices_tensor(n, epoch, rank, world, shuffle, seed, drop_last).numpy()
 
 
+def blur_kernel_from_cfg(cfg, out_size: int) -> int:
+    """Training loaders' ``blur_kernel`` from the opt-in keys: 0 unless ``data.blur`` is set;
+    ``data.blur_kernel`` (0: SimCLR's 10 % of the side, 3 at 32, 7 at 64, 23 at 224) otherwise."""
+    if not bool(cfg_get(cfg, "data.blur", False)):
+        return 0
+    ks = int(cfg_get(cfg, "data.blur_kernel", 0) or 0)
+    ks = ks or augment_ref.default_blur_kernel(out_size)
+    augment_ref.check_blur_kernel(ks, out_size, out_size)
+    return ks
+
+
 class ContrastiveLoader:
     """Iterates ``(x, labels)`` per step; x = both augmented views of the rank's batch."""
 
@@ -60,7 +72,7 @@ class ContrastiveLoader:
                  rank: int = 0, world: int = 1, strength: float = 0.5, seed: int = 0,
                  views: int = 2, out_size: Optional[int] = None, augment: bool = True,
                  shuffle: bool = True, drop_last: bool = True, sampler_seed: int = 0,
-                 use_gpu_kernel: Optional[bool] = None):
+                 use_gpu_kernel: Optional[bool] = None, blur_kernel: int = 0):
         self.ds = dataset
         self.n = batch_size
         self.device = torch.device(device)
@@ -72,6 +84,11 @@ class ContrastiveLoader:
         self.OH = out_size or self.H
         self.OW = out_size or self.W
         self.augment = augment
+        # SimCLR's Gaussian blur (kernel size; 0: off), the last op of the augmentation
+        self.blur_kernel = int(blur_kernel)
+        augment_ref.check_blur_kernel(self.blur_kernel, self.OH, self.OW)
+        if self.blur_kernel and not augment:
+            raise ValueError("blur_kernel needs augment=True")
         self.shuffle = shuffle
         self.drop_last = drop_last
         self.sampler_seed = sampler_seed
@@ -113,11 +130,12 @@ class ContrastiveLoader:
                                   memory_format=torch.channels_last)
             torch.ops.simclr_amd.augment(self.images, idx, n, self.views, self.OH, self.OW, CPAD,
                                          self.strength, self.seed, counter, 0,
-                                         1 if self.augment else 0, out.permute(0, 2, 3, 1), None)
+                                         1 if self.augment else 0, out.permute(0, 2, 3, 1), None,
+                                         self.blur_kernel)
             return out
         arr = augment_ref.augment_batch(self.images, idx.cpu().numpy(), self.views, self.OH,
                                         self.OW, self.strength, self.seed, counter,
-                                        augment=self.augment)
+                                        augment=self.augment, blur_kernel=self.blur_kernel)
         return torch.from_numpy(arr)
 
     def epoch_indices(self) -> torch.Tensor:

@@ -35,7 +35,7 @@ import torch.distributed as dist
 from ..comm.ipc import StepGuard
 from ..config import check_pretrain_conf
 from ..data.datasets import load_dataset
-from ..data.loader import ContrastiveLoader
+from ..data.loader import ContrastiveLoader, blur_kernel_from_cfg
 from ..loss.ntxent import NTXent
 from ..models.contrastive import ContrastiveModel
 from ..ops import registry
@@ -258,7 +258,8 @@ def pretrain(cfg) -> dict:
                       seed=seed)
     loader = ContrastiveLoader(ds, cfg["experiment"]["batches"], st.device, rank=rank,
                                world=st.world_size, strength=cfg["experiment"]["strength"],
-                               seed=seed, views=2)
+                               seed=seed, views=2,
+                               blur_kernel=blur_kernel_from_cfg(cfg, ds.images.shape[1]))
     loader.with_labels = False  # SimCLR pre-training uses no labels
     tr = Trainer(cfg, st, len(ds))
     epochs = cfg["parameter"]["epochs"]

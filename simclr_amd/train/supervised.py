@@ -23,7 +23,7 @@ import torch.distributed as dist
 from ..comm.ipc import StepGuard
 from ..config import check_supervised_conf
 from ..data.datasets import load_dataset
-from ..data.loader import ContrastiveLoader
+from ..data.loader import ContrastiveLoader, blur_kernel_from_cfg
 from ..models.contrastive import SupervisedModel
 from ..ops import registry
 from ..ops.classify import ce_rank, cross_entropy
@@ -84,7 +84,9 @@ def supervised(cfg) -> dict:
                           synthetic_size=(max(1, size // 5) if size else None), **kw)
     bs = cfg["experiment"]["batches"]
     train_loader = ContrastiveLoader(train_ds, bs, dev, rank=st.rank, world=st.world_size,
-                                     strength=cfg["experiment"]["strength"], seed=seed, views=1)
+                                     strength=cfg["experiment"]["strength"], seed=seed, views=1,
+                                     blur_kernel=blur_kernel_from_cfg(cfg,
+                                                                      train_ds.images.shape[1]))
     val_loader = ContrastiveLoader(val_ds, bs, dev, rank=st.rank, world=st.world_size, views=1,
                                    augment=False, shuffle=False, drop_last=False)
     model = SupervisedModel(cfg["experiment"]["base_cnn"], num_classes=train_ds.num_classes,
