@@ -38,8 +38,37 @@ def check_pretrain_conf(cfg) -> None:
     _check(e["decay"] >= 0.0, "experiment.decay must be >= 0")
 
 
+def _check_sweep(cfg) -> None:
+    """The opt-in ``parameter.sweep_lr`` / ``parameter.sweep_decay`` lists of the linear probe,
+    within the sweep op's limits (``ops.probe_sweep.check_limits``)."""
+    from ..ops import probe_sweep
+    p, e = cfg["parameter"], cfg["experiment"]
+    lrs, decays = p.get("sweep_lr"), p.get("sweep_decay")
+    if lrs is None and decays is None:
+        return
+    _check(p.get("classifier") == "linear",
+           "parameter.sweep_lr / parameter.sweep_decay need parameter.classifier=linear")
+    for key, vals in (("parameter.sweep_lr", lrs), ("parameter.sweep_decay", decays)):
+        if vals is None:
+            continue
+        _check(isinstance(vals, (list, tuple)) and len(vals) > 0,
+               f"{key} must be a non-empty list")
+        _check(all(isinstance(v, (int, float)) and not isinstance(v, bool) for v in vals),
+               f"{key} must hold numbers")
+    _check(lrs is None or all(v > 0.0 for v in lrs), "parameter.sweep_lr: every lr must be > 0")
+    _check(decays is None or all(v >= 0.0 for v in decays),
+           "parameter.sweep_decay: every decay must be >= 0")
+    G = len(lrs or [0]) * len(decays or [0])
+    classes = {"cifar10": 10, "cifar100": 100}.get(e.get("name"))
+    try:
+        probe_sweep.check_limits(G, classes, None, e["batches"])
+    except ValueError as err:
+        raise AssertionError(str(err)) from None
+
+
 def check_eval_conf(cfg) -> None:
     p, e = cfg["parameter"], cfg["experiment"]
+    _check_sweep(cfg)
     _check(p["epochs"] > 0, "parameter.epochs must be > 0")
     _check(e["batches"] > 0, "experiment.batches must be > 0")
     _check(1.0 > p["momentum"] > 0.0, "parameter.momentum must be in (0, 1)")

@@ -1144,10 +1144,125 @@ void knn_vote_op(const Tensor& vals, const Tensor& idx, const Tensor& labels, in
            f32w(scores, "scores"), rank.data_ptr<int>(), cur_stream());
 }
 
+// ------------------------------------------------------------------------------- probe sweep
+// shared geometry checks: X [N][Fp] bf16, idx [rows] int64, G configurations of C classes
+int64_t probe_geometry(const char* op, const Tensor& X, const Tensor& idx, const Tensor& Wsh,
+                       int64_t G, int64_t C) {
+  TORCH_CHECK(X.dim() == 2 && Wsh.dim() == 2, op, ": X [N][Fp], Wsh [G * Cp][Fp]");
+  const int64_t N = X.size(0), Fp = X.size(1), rows = idx.numel();
+  TORCH_CHECK(N >= 1 && N < (1ll << 31), op, ": N must be in [1, 2^31)");
+  TORCH_CHECK(Fp >= probe_kstep() && Fp % probe_kstep() == 0 && Fp <= 4096, op,
+              ": padded feature width must be a multiple of ", probe_kstep(), " and <= 4096, got ",
+              Fp);
+  TORCH_CHECK(G >= 1 && G <= probe_max_configs(), op, ": G must be in [1, ", probe_max_configs(),
+              "], got ", G);
+  TORCH_CHECK(C >= 1, op, ": C must be >= 1");
+  const int64_t Cp = (C + 15) / 16 * 16;
+  TORCH_CHECK(G * Cp <= probe_max_cols(), op, ": G * Cp must be <= ", probe_max_cols(), ", got ",
+              G * Cp);
+  TORCH_CHECK(rows >= 1 && rows <= probe_max_rows(), op, ": rows must be in [1, ",
+              probe_max_rows(), "], got ", rows);
+  TORCH_CHECK(Wsh.size(0) == G * Cp && Wsh.size(1) == Fp, op, ": Wsh must be [", G * Cp, "][", Fp,
+              "]");
+  check_dev(idx, at::kLong, "idx");
+  return Cp;
+}
+
+void probe_forward_op(const Tensor& X, const Tensor& y, const Tensor& idx, const Tensor& Wsh,
+                      const Tensor& bias, int64_t G, int64_t C, const Tensor& Z,
+                      const Tensor& loss, int64_t loss_stride, const c10::optional<Tensor>& rank,
+                      const c10::optional<Tensor>& dlT, const c10::optional<Tensor>& dbp) {
+  const int64_t Cp = probe_geometry("probe_forward", X, idx, Wsh, G, C);
+  const int64_t N = X.size(0), rows = idx.numel(), NT = G * Cp;
+  const bool train = dlT.has_value() && dlT->defined();
+  const int64_t Rp = train ? (rows + 31) / 32 * 32 : (rows + 15) / 16 * 16;
+  check_dev(y, at::kLong, "y");
+  TORCH_CHECK(y.numel() == N, "probe_forward: y [N]");
+  TORCH_CHECK(bias.numel() == NT, "probe_forward: bias [G * Cp]");
+  TORCH_CHECK(Z.numel() >= rows * NT, "probe_forward: logits scratch [rows][G * Cp]");
+  TORCH_CHECK(loss_stride >= rows && loss.numel() >= (G - 1) * loss_stride + rows,
+              "probe_forward: loss [G][loss_stride >= rows]");
+  ProbeFwdArgs a{};
+  a.X = bf(X, "X");
+  a.y = y.data_ptr<int64_t>();
+  a.idx = idx.data_ptr<int64_t>();
+  a.N = N;
+  a.Fp = (int)X.size(1);
+  a.rows = (int)rows;
+  a.Rp = (int)Rp;
+  a.G = (int)G;
+  a.C = (int)C;
+  a.Cp = (int)Cp;
+  a.Wsh = bf(Wsh, "Wsh");
+  a.bias = f32(bias, "bias");
+  a.Z = f32w(Z, "Z");
+  a.loss = f32w(loss, "loss");
+  a.loss_stride = loss_stride;
+  if (rank.has_value() && rank->defined()) {
+    check_dev(*rank, at::kInt, "rank");
+    TORCH_CHECK(rank->numel() == G * rows, "probe_forward: rank [G][rows]");
+    a.rank = rank->data_ptr<int>();
+  }
+  if (train) {
+    TORCH_CHECK(dlT->dim() == 2 && dlT->size(0) == NT && dlT->size(1) >= Rp &&
+                    dlT->size(1) % 32 == 0,
+                "probe_forward: dlT [G * Cp][>= rows rounded up to 32, a multiple of 32]");
+    TORCH_CHECK(dbp.has_value() && dbp->defined() && dbp->numel() >= (rows + 15) / 16 * NT,
+                "probe_forward: dbp [ceil(rows / 16)][G * Cp]");
+    a.dlT = bfw(*dlT, "dlT");
+    a.ldr = (int)dlT->size(1);
+    a.dbp = f32w(*dbp, "dbp");
+  }
+  probe_forward(a, cur_stream());
+}
+
+void probe_update_op(const Tensor& X, const Tensor& idx, const Tensor& dlT, const Tensor& dbp,
+                     const Tensor& W, const Tensor& Mw, const Tensor& Wsh, const Tensor& b,
+                     const Tensor& Mb, const Tensor& lr0, const Tensor& wd, const Tensor& ftab,
+                     int64_t step, double momentum, int64_t G, int64_t C) {
+  const int64_t Cp = probe_geometry("probe_update", X, idx, Wsh, G, C);
+  const int64_t rows = idx.numel(), NT = G * Cp, Fp = X.size(1);
+  const int64_t Rp = (rows + 31) / 32 * 32;
+  TORCH_CHECK(dlT.dim() == 2 && dlT.size(0) == NT && dlT.size(1) >= Rp && dlT.size(1) % 32 == 0,
+              "probe_update: dlT [G * Cp][>= rows rounded up to 32, a multiple of 32]");
+  TORCH_CHECK(dbp.numel() >= (rows + 15) / 16 * NT, "probe_update: dbp");
+  TORCH_CHECK(W.numel() == NT * Fp && Mw.numel() == NT * Fp, "probe_update: W, Mw [G * Cp][Fp]");
+  TORCH_CHECK(b.numel() == NT && Mb.numel() == NT, "probe_update: b, Mb [G * Cp]");
+  TORCH_CHECK(lr0.numel() == G && wd.numel() == G, "probe_update: lr0, wd [G]");
+  TORCH_CHECK(step >= 0 && step < ftab.numel(), "probe_update: step ", step,
+              " outside the schedule table of ", ftab.numel());
+  ProbeUpdArgs a{};
+  a.X = bf(X, "X");
+  a.idx = idx.data_ptr<int64_t>();
+  a.N = X.size(0);
+  a.Fp = (int)Fp;
+  a.rows = (int)rows;
+  a.Rp = (int)Rp;
+  a.G = (int)G;
+  a.C = (int)C;
+  a.Cp = (int)Cp;
+  a.dlT = bf(dlT, "dlT");
+  a.ldr = (int)dlT.size(1);
+  a.dbp = f32(dbp, "dbp");
+  a.W = f32w(W, "W");
+  a.Mw = f32w(Mw, "Mw");
+  a.b = f32w(b, "b");
+  a.Mb = f32w(Mb, "Mb");
+  a.Wsh = bfw(Wsh, "Wsh");
+  a.lr0 = f32(lr0, "lr0");
+  a.wd = f32(wd, "wd");
+  a.ftab = f32(ftab, "ftab");
+  a.step = (int)step;
+  a.momentum = (float)momentum;
+  probe_update(a, cur_stream());
+}
+
 }  // namespace
 
 
 TORCH_LIBRARY(simclr_amd, m) {
+  m.def("probe_forward(Tensor X, Tensor y, Tensor idx, Tensor Wsh, Tensor bias, int G, int C, Tensor(a!) Z, Tensor(b!) loss, int loss_stride, Tensor(c!)? rank, Tensor(d!)? dlT, Tensor(e!)? dbp) -> ()", &probe_forward_op);
+  m.def("probe_update(Tensor X, Tensor idx, Tensor dlT, Tensor dbp, Tensor(a!) W, Tensor(b!) Mw, Tensor(c!) Wsh, Tensor(d!) b, Tensor(e!) Mb, Tensor lr0, Tensor wd, Tensor ftab, int step, float momentum, int G, int C) -> ()", &probe_update_op);
   m.def("knn_normalize(Tensor x, Tensor(a!) out) -> ()", &knn_normalize_op);
   m.def("knn_topk(Tensor qn, Tensor bn, int k, bool exclude_self, int self_offset, Tensor(a!) vals, Tensor(b!) idx) -> ()", &knn_topk_op);
   m.def("knn_scratch_bytes(int Q, int N, int k) -> int", &knn_scratch_bytes_op);

@@ -279,3 +279,44 @@ void knn_topk(const uint16_t* Qn, const uint16_t* Bn, int Q, int N, int Dp, int 
               int* idx, hipStream_t s);
 void knn_vote(const float* vals, const int* idx, const int64_t* labels, const int64_t* targets,
               int Q, int k, int N, int C, float inv_t, float* scores, int* rank, hipStream_t s);
+
+// ---- probe.hip: linear-probe sweep (G classifiers on one feature batch: fused forward / CE /
+// gradient, fused weight gradient / Nesterov SGD update)
+int probe_kstep();        // Fp is F rounded up to this
+int probe_max_configs();  // G
+int probe_max_cols();     // G * Cp
+int probe_max_rows();     // rows of one call
+struct ProbeFwdArgs {
+  const uint16_t* X;      // [N][Fp] bf16 features
+  const int64_t* y;       // [N] labels
+  const int64_t* idx;     // [rows] gathered feature rows
+  long long N;
+  int Fp, rows, Rp;       // Rp: rows rounded up to 32 (training) or 16 (evaluation)
+  int G, C, Cp;
+  const uint16_t* Wsh;    // [G * Cp][Fp] bf16 shadow weights
+  const float* bias;      // [G * Cp]
+  float* Z;               // [>= rows][G * Cp] logits scratch
+  float* loss;            // loss[g * loss_stride + row]
+  long long loss_stride;
+  int* rank;              // [G][rows] or null
+  uint16_t* dlT;          // [G * Cp][ldr] bf16 or null (evaluation)
+  int ldr;
+  float* dbp;             // [ceil(rows / 16)][G * Cp] bias-gradient partials
+};
+void probe_forward(const ProbeFwdArgs& a, hipStream_t s);
+struct ProbeUpdArgs {
+  const uint16_t* X;
+  const int64_t* idx;
+  long long N;
+  int Fp, rows, Rp, G, C, Cp;
+  const uint16_t* dlT;
+  int ldr;
+  const float* dbp;
+  float *W, *Mw, *b, *Mb;  // fp32 master and momentum
+  uint16_t* Wsh;
+  const float *lr0, *wd;   // [G]
+  const float* ftab;       // cosine factors per step
+  int step;
+  float momentum;
+};
+void probe_update(const ProbeUpdArgs& a, hipStream_t s);

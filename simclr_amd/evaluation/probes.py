@@ -10,7 +10,11 @@ Parity: ``centroid_eval`` (``/root/reference/eval.py:61-85``), ``learnable_eval`
 * linear / nonlinear: SGD(lr = lr·batches/256, momentum, **nesterov=True**, wd = decay),
   ``CosineAnnealingLR(T_max = epochs·ceil(N/batches))`` stepped every batch, shuffled batches;
   after every epoch train and val (top-1, top-k, mean CE) are recomputed; the JSON reports the
-  per-epoch lists and ``lowest_val_loss``, ``highest_val_acc``, ``highest_val_top_k_acc``.
+  per-epoch lists and ``lowest_val_loss``, ``highest_val_acc``, ``highest_val_top_k_acc``;
+* linear with ``parameter.sweep_lr`` / ``parameter.sweep_decay`` (not in the reference): the grid
+  of lr x weight decay trained in one pass (``sweep_eval``, contract in ``ops/probe_sweep.py``);
+  the JSON holds one linear entry per configuration under ``sweep``, the ``best`` index and that
+  entry's fields at the top level.
 
 Fixed reference defects: ``top_k <= 1`` no longer accumulates cumulative top-1 counts (Q4), and
 ``NonLinearClassifier`` exists (Q1).  Features and labels stay on the device; batches are index
@@ -28,6 +32,7 @@ import torch.nn.functional as F
 
 from ..models.heads import CentroidClassifier, LinearClassifier, NonLinearClassifier
 from ..ops.classify import ce_rank, cross_entropy
+from ..ops import probe_sweep
 from ..ops.knn import knn_topk, knn_vote
 from ..utils.misc import cfg_get
 from ..optim.schedule import cosine_lr
@@ -167,6 +172,83 @@ def learnable_eval(cfg, classifier, train: DownstreamDataset, val: DownstreamDat
     return tr_acc, tr_topk, tr_loss, va_acc, va_topk, va_loss
 
 
+def sweep_values(cfg) -> Tuple[List[float], List[float]] | None:
+    """(lrs, decays) of ``parameter.sweep_lr`` / ``parameter.sweep_decay``, an unset key meaning the
+    one value of ``experiment.lr`` / ``experiment.decay``; ``None`` without either key."""
+    lrs, decays = cfg_get(cfg, "parameter.sweep_lr", None), cfg_get(cfg, "parameter.sweep_decay", None)
+    if lrs is None and decays is None:
+        return None
+    e = cfg["experiment"]
+    return ([float(v) for v in lrs] if lrs is not None else [float(e["lr"])],
+            [float(v) for v in decays] if decays is not None else [float(e["decay"])])
+
+
+@torch.no_grad()
+def sweep_eval(cfg, classifier: LinearClassifier, train: DownstreamDataset, val: DownstreamDataset,
+               lrs: List[float], decays: List[float], top_k: int = 5, seed: int = 0,
+               round_operands: bool = True, accumulate: torch.dtype = torch.float32,
+               hip: bool | None = None):
+    """``learnable_eval`` for the grid ``lrs`` x ``decays`` in one pass over the shuffled features
+    (``ops/probe_sweep.py`` holds the contract).  Every configuration starts from ``classifier``'s
+    weights and sees the batches an unswept run with the same seed sees.  Returns (one
+    ``learnable_eval`` tuple per configuration, decay-major and lr-minor; the ``LinearSweep``)."""
+    p, e = cfg["parameter"], cfg["experiment"]
+    epochs, bs, n = p["epochs"], e["batches"], len(train)
+    configs = probe_sweep.grid(lrs, decays)
+    lin = classifier.classifier
+    probe_sweep.check_limits(len(configs), lin.out_features, lin.in_features, bs)
+    total_steps = epochs * int(math.ceil(n / bs))
+    dev = train.data.device
+    lr0 = probe_sweep.initial_lrs([c[0] for c in configs], bs, bool(p["linear_schedule"]))
+    sweep = probe_sweep.LinearSweep(lin.weight, lin.bias, lr0, [c[1] for c in configs],
+                                    p["momentum"], probe_sweep.cosine_table(total_steps),
+                                    device=dev, round_operands=round_operands,
+                                    accumulate=accumulate, hip=hip)
+    Xtr = probe_sweep.prepare_features(train.data, round_operands)
+    Xva = probe_sweep.prepare_features(val.data.to(dev), round_operands)
+    ytr = train.targets.to(device=dev, dtype=torch.long).contiguous()
+    yva = val.targets.to(device=dev, dtype=torch.long).contiguous()
+    gen = torch.Generator()
+    gen.manual_seed(seed)
+    G = len(configs)
+    out = [([], [], [], [], [], []) for _ in range(G)]
+    losses = torch.empty(G, n, device=dev, dtype=torch.float32)
+    for epoch in range(1, epochs + 1):
+        pos = 0
+        for idx in _batches(n, bs, True, gen, dev):
+            sweep.train_step(Xtr, ytr, idx, losses, pos)
+            pos += len(idx)
+        mean = (losses.double().sum(1) / n).cpu().tolist()
+        logging.info("Epoch:{}/{} progress:{:.3f} loss:[{}]".format(
+            epoch, epochs, epoch / epochs, ", ".join("{:.3f}".format(v) for v in mean)))
+        tl, t1, tk = sweep.evaluate(Xtr, ytr, top_k)
+        vl, v1, vk = sweep.evaluate(Xva, yva, top_k)
+        for g in range(G):
+            for lst, v in zip(out[g], (t1[g], tk[g], tl[g], v1[g], vk[g], vl[g])):
+                lst.append(v)
+    return out, sweep
+
+
+def _nanmin(v: List[float]) -> float:
+    ok = [x for x in v if x == x]
+    return min(ok) if ok else float("nan")
+
+
+def _linear_result(t, top_k: int) -> Dict:
+    tr_acc, tr_topk, tr_loss, va_acc, va_topk, va_loss = t
+    return {
+        "train_accuracies": tr_acc,
+        "val_accuracies": va_acc,
+        "train_losses": tr_loss,
+        "val_losses": va_loss,
+        "train_top_{}_accuracies".format(top_k): tr_topk,
+        "val_top_{}_accuracies".format(top_k): va_topk,
+        "lowest_val_loss": _nanmin(va_loss),
+        "highest_val_acc": max(va_acc),
+        "highest_val_top_k_acc": max(va_topk),
+    }
+
+
 def run_probe(cfg, kind: str, train: DownstreamDataset, val: DownstreamDataset, num_classes: int,
               top_k: int, device) -> Dict:
     if kind == "centroid":
@@ -201,6 +283,19 @@ def run_probe(cfg, kind: str, train: DownstreamDataset, val: DownstreamDataset, 
         clf = NonLinearClassifier(F_, num_classes).to(device)
     else:
         raise ValueError(f"unknown classifier {kind!r} (centroid | knn | linear | nonlinear)")
+    sv = sweep_values(cfg)
+    if sv is not None:
+        if kind != "linear":
+            raise ValueError("parameter.sweep_lr / parameter.sweep_decay need parameter.classifier=linear")
+        per_cfg, _ = sweep_eval(cfg, clf, train, val, sv[0], sv[1], top_k,
+                                seed=cfg["parameter"]["seed"])
+        entries = []
+        for (lr, decay), t in zip(probe_sweep.grid(*sv), per_cfg):
+            entries.append(dict(_linear_result(t, top_k), lr=lr, decay=decay))
+        best = max(range(len(entries)), key=lambda i: (entries[i]["highest_val_acc"], -i))
+        logging.info("sweep best: lr {} decay {} val acc {}".format(
+            entries[best]["lr"], entries[best]["decay"], entries[best]["highest_val_acc"]))
+        return dict(entries[best], sweep=entries, best=best)
     tr_acc, tr_topk, tr_loss, va_acc, va_topk, va_loss = learnable_eval(
         cfg, clf, train, val, top_k, seed=cfg["parameter"]["seed"])
     logging.info("train acc: {}, val acc: {}".format(max(tr_acc), max(va_acc)))
