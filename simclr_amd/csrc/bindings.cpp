@@ -134,11 +134,14 @@ void igemm(const Tensor& A, const Tensor& B, const Tensor& out, const c10::optio
     TORCH_CHECK(igemm_dual_ok((int)variant, g),
                 "igemm: block-output prologue needs a 2-stage LDS-DMA variant (igemm_dual_ok) on "
                 "a 1x1 / stride-1 / unpadded convolution");
-  } else if (igemm_variant_glds((int)variant)) {
-    TORCH_CHECK(igemm_variant_ok((int)variant, g, pro_sc.has_value() && pro_sc->defined(),
-                                 pro_d.has_value() && pro_d->defined()),
-                "igemm: LDS-DMA variant needs C % 64 == 0 and its prologues (BN-apply, "
-                "BN-backward) only on unpadded 1x1 convolutions (2-stage tiles whose staging fits)");
+  } else {
+    TORCH_CHECK(igemm_variant_ok((int)variant, g, pro_sc.has_value() && pro_sc->defined(), has_pd,
+                                 (int)epi_mode),
+                "igemm: variant ", variant, " is not admissible here: an LDS-DMA variant needs "
+                "C % 64 == 0, its prologues (BN-apply, BN-backward) only on unpadded 1x1 "
+                "convolutions (2-stage tiles whose staging fits) and, for the BN-backward prologue "
+                "with the mode-4 epilogue, a tile of at most 256 x 128; a patch variant needs its "
+                "3x3 stride-1 geometry");
   }
   if (bias.has_value() && bias->defined()) TORCH_CHECK(bias->numel() == g.N, "igemm: bias size");
   const bool has_stats = stats.has_value() && stats->defined();
@@ -211,16 +214,13 @@ void igemm(const Tensor& A, const Tensor& B, const Tensor& out, const c10::optio
   }
   if (pro_d.has_value() && pro_d->defined()) {
     TORCH_CHECK(f.pro_sc, "igemm BN-backward prologue needs pro_sc (A) and pro_sh (B)");
-    // the BN-backward prologue + mode-4 epilogue is not instantiated for tiles above 256 x 128
-    // (the 256 x 256 tile with both fusions drains its DMA pipeline): conv.hip launch_glds
-    TORCH_CHECK(!(igemm_variant_glds((int)variant) && epi_mode == 4 &&
-                  igemm_variant_bm((int)variant) * igemm_variant_bn((int)variant) > 256 * 128),
-                "igemm: BN-backward prologue + mode-4 epilogue needs an LDS-DMA tile of at most "
-                "256 x 128 (variant ", variant, ")");
     TORCH_CHECK(pro_d->numel() >= (M / pro_seg_rows) * g.C, "igemm prologue: d [S][C] size");
     TORCH_CHECK(A2.has_value() && A2->numel() == A.numel(), "igemm prologue: A2 must match A");
     TORCH_CHECK(epi_mode == 0 || epi_mode == 3 || epi_mode == 4,
                 "igemm BN-backward prologue: epilogue 0, 3 or 4");
+    // (igemm_patch has this prologue with the plain and mode-3 epilogues only)
+    TORCH_CHECK(!(igemm_variant_patch((int)variant) && epi_mode == 4),
+                "igemm BN-backward prologue on a patch variant: epilogue 0 or 3");
     f.pro_d = f32(*pro_d, "pro_d");
     f.A2 = bf(*A2, "A2");
     if (pro_out.has_value() && pro_out->defined()) {
@@ -285,8 +285,8 @@ bool igemm_gldsok(std::vector<int64_t> gv, bool pro, bool bn_bwd_pro) {
 int64_t wgrad_nvariants() { return wgrad_num_variants(); }
 int64_t wgrad_xlin_op(int64_t mode) { return wgrad_xlin((int)mode); }
 bool wgrad_vglds(int64_t v) { return wgrad_variant_glds((int)v); }
-bool igemm_vok(int64_t v, std::vector<int64_t> gv, bool pro, bool bnb) {
-  return igemm_variant_ok((int)v, geom_from(gv), pro, bnb);
+bool igemm_vok(int64_t v, std::vector<int64_t> gv, bool pro, bool bnb, int64_t epi_mode) {
+  return igemm_variant_ok((int)v, geom_from(gv), pro, bnb, (int)epi_mode);
 }
 bool igemm_dok(int64_t v, std::vector<int64_t> gv) { return igemm_dual_ok((int)v, geom_from(gv)); }
 bool wgrad_vok(int64_t v, std::vector<int64_t> gv, bool pro, bool dpro) {
@@ -316,11 +316,13 @@ void wgrad(const Tensor& dY, const Tensor& X, const Tensor& partial, const Tenso
   TORCH_CHECK(out.numel() == (int64_t)g.N * g.KH * g.KW * creal, "wgrad: out numel mismatch");
   TORCH_CHECK(creal <= g.C && creal > 0, "wgrad: bad creal");
   TORCH_CHECK(pro_S >= 1 && pro_S <= 2, "wgrad prologue supports at most 2 segments");
-  if (wgrad_variant_glds((int)variant))
-    TORCH_CHECK(wgrad_variant_ok((int)variant, g, pro_sc.has_value() && pro_sc->defined(),
-                                 dY2.has_value() && dY2->defined()),
-                "wgrad: LDS-DMA variant needs C % 64 == 0, no dY prologue, and an X prologue only "
-                "on unpadded 1x1 convolutions");
+  if (variant < 0 || variant >= wgrad_num_variants()) variant = wgrad_default_variant(g.N);
+  TORCH_CHECK(wgrad_variant_ok((int)variant, g, pro_sc.has_value() && pro_sc->defined(),
+                               dY2.has_value() && dY2->defined()),
+              "wgrad: variant ", variant, " is not admissible here: an LDS-DMA variant needs "
+              "C % 64 == 0, no dY prologue, and an X prologue only on unpadded 1x1 convolutions "
+              "(wgrad_pipe / wgrad_xp: none); the patch variant needs its 3x3 stride-1 geometry, "
+              "N % 64 == 0 and no dY prologue");
   ConvFusion f = fusion_from(pro_sc, pro_sh, pro_seg_rows, pro_relu, pro_S, 0, c10::nullopt,
                              c10::nullopt, g.C, 0);
   if (f.pro_sc) {
@@ -337,8 +339,6 @@ void wgrad(const Tensor& dY, const Tensor& X, const Tensor& partial, const Tenso
                     (dp_S <= 2 || dp_seg_rows % (ips * 64) == 0) && dp_seg_rows % 64 == 0,
                 "wgrad dY prologue: 64-row segments, and every split inside one segment when "
                 "there are more than two");
-    TORCH_CHECK(!wgrad_variant_glds((int)variant),
-                "wgrad dY prologue: register-staged variants only");
     f.dY2 = bf(*dY2, "dY2");
     f.dp_coef = f32(*dp_coef, "dp_coef");
     f.dp_seg_rows = (int)dp_seg_rows;
@@ -1290,14 +1290,13 @@ TORCH_LIBRARY(simclr_amd, m) {
   m.def("wgrad_nvariants() -> int", &wgrad_nvariants);
   m.def("wgrad_xlin(int mode=-1) -> int", &wgrad_xlin_op);
   m.def("wgrad_variant_glds(int v) -> bool", &wgrad_vglds);
-  m.def("igemm_variant_patch(int v) -> bool", [](int64_t v) {
-    return v >= 0 && v < igemm_num_variants() && igemm_variant_patch((int)v);
-  });
+  m.def("igemm_variant_patch(int v) -> bool", [](int64_t v) { return igemm_variant_patch((int)v); });
   m.def("wgrad_variant_area(int v) -> int", [](int64_t v) -> int64_t {
     TORCH_CHECK(v >= 0 && v < wgrad_num_variants(), "wgrad variant out of range");
     return wgrad_variant_area((int)v);
   });
-  m.def("igemm_variant_ok(int v, int[] geom, bool pro, bool bn_bwd_pro) -> bool", &igemm_vok);
+  m.def("igemm_variant_ok(int v, int[] geom, bool pro, bool bn_bwd_pro, int epi_mode=0) -> bool",
+        &igemm_vok);
   m.def("wgrad_variant_ok(int v, int[] geom, bool pro, bool dy_pro) -> bool", &wgrad_vok);
   m.def("wgrad_splits(int[] geom, int variant=-1) -> int", &wgrad_nsplit);
   m.def("wgrad_tiles(int[] geom, int variant=-1) -> int", &wgrad_ntiles);

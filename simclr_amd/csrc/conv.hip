@@ -29,6 +29,7 @@
 #include "kernels.h"
 
 #include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -2609,143 +2610,78 @@ void launch_patch_t(const IgemmArgs& a0, hipStream_t s) {
   HIP_CHECK_LAUNCH();
 }
 
-template <int BN, int WM, int WN>
-void launch_patch(const IgemmArgs& a, hipStream_t s) {
-  if (a.pro_d != nullptr) {  // BN-backward prologue on the landed patch: plain or mode-3 epilogue
-    if (a.epi_mode == 3)
-      launch_patch_t<BN, WM, WN, 3, 2>(a, s);
-    else
-      launch_patch_t<BN, WM, WN, 0, 2>(a, s);
-    return;
+// ---- compile-time fusion modes (prologue x epilogue), so each launch carries only its own work
+// PRO: 0 none, 1 BN-apply, 2 BN-backward, 3 block-output.  EPI: epi_mode, 5 = mode 4 with the
+// second BN stream.  igemm_fusion_allowed is the set of pairs a kernel family instantiates for a
+// tile; the launchers and the host admissibility (igemm_variant_ok / igemm_dual_ok) both read it.
+enum IgFam { IG_NT, IG_GLDS, IG_PATCH };  // register-staged igemm_nt, LDS-DMA igemm_glds, igemm_patch
+constexpr int kNumPro = 4, kNumEpi = 6;
+constexpr bool igemm_fusion_allowed(IgFam fam, int pro, int epi, int area, int stages) {
+  if (pro == 0) return true;                  // every epilogue
+  const bool bwd = epi == 0 || epi == 3;      // what every BN-backward prologue has
+  switch (fam) {
+    case IG_NT:  // BN-apply: no mode 4; no block-output prologue
+      return pro == 1 ? epi <= 3 : pro == 2 && (bwd || epi >= 4);
+    case IG_GLDS:
+      // the 3-stage tiles leave no LDS for the prologue table; the single-stage ones have the
+      // BN-apply prologue only; the block-output prologue takes the plain epilogue; a tile above
+      // 256 x 128 with the BN-backward prologue and mode 4 drains its DMA pipeline
+      if (pro == 1) return stages <= 2 && epi <= 3;
+      if (stages != 2) return false;
+      return pro == 2 ? bwd || (epi >= 4 && area <= 256 * 128) : epi == 0;
+    case IG_PATCH:  // prologues on the landed patch: BN-apply with any epilogue
+      return pro == 1 || (pro == 2 && bwd);
   }
-  if (a.pro_sc != nullptr) {  // BN-apply prologue on the landed patch, any epilogue
-    switch (a.epi_mode) {
-      case 1: launch_patch_t<BN, WM, WN, 1, 1>(a, s); break;
-      case 2: launch_patch_t<BN, WM, WN, 2, 1>(a, s); break;
-      case 3: launch_patch_t<BN, WM, WN, 3, 1>(a, s); break;
-      case 4:
-        if (a.stats2 != nullptr)
-          launch_patch_t<BN, WM, WN, 5, 1>(a, s);
-        else
-          launch_patch_t<BN, WM, WN, 4, 1>(a, s);
-        break;
-      default: launch_patch_t<BN, WM, WN, 0, 1>(a, s); break;
-    }
-    return;
-  }
-  switch (a.epi_mode) {
-    case 1: launch_patch_t<BN, WM, WN, 1>(a, s); break;
-    case 2: launch_patch_t<BN, WM, WN, 2>(a, s); break;
-    case 3: launch_patch_t<BN, WM, WN, 3>(a, s); break;
-    case 4:
-      if (a.stats2 != nullptr)
-        launch_patch_t<BN, WM, WN, 5>(a, s);
-      else
-        launch_patch_t<BN, WM, WN, 4>(a, s);
-      break;
-    default: launch_patch_t<BN, WM, WN, 0>(a, s); break;
-  }
+  return false;
+}
+inline int igemm_pro_code(bool bn_apply, bool bn_bwd, bool block_out) {
+  return bn_bwd ? 2 : block_out ? 3 : bn_apply ? 1 : 0;
 }
 
+template <IgFam FAM, int AREA, int STAGES, int I, class F>
+bool launch_fusion_if(int pro, int epi, const IgemmArgs& a, hipStream_t s, F f) {
+  constexpr int PRO = I / kNumEpi, EPI = I % kNumEpi;
+  if constexpr (igemm_fusion_allowed(FAM, PRO, EPI, AREA, STAGES)) {
+    if (pro == PRO && epi == EPI) {
+      f(std::integral_constant<int, PRO>{}, std::integral_constant<int, EPI>{}, a, s);
+      return true;
+    }
+  }
+  return false;
+}
+// launch f(PRO, EPI, a, s) with the pair these arguments ask for
+template <IgFam FAM, int AREA, int STAGES, class F, int... I>
+void launch_fusion(const IgemmArgs& a, hipStream_t s, F f, std::integer_sequence<int, I...>) {
+  const int pro = igemm_pro_code(a.pro_sc != nullptr, a.pro_d != nullptr, a.pro_out != nullptr);
+  const int epi = a.epi_mode == 4 && a.stats2 != nullptr ? 5
+                  : a.epi_mode >= 1 && a.epi_mode <= 4   ? a.epi_mode
+                                                         : 0;
+  if (!(launch_fusion_if<FAM, AREA, STAGES, I>(pro, epi, a, s, f) || ...)) {
+    fprintf(stderr, "igemm: unsupported fusion (prologue %d, epilogue %d) on this tile\n", pro, epi);
+    abort();  // the bindings reject this
+  }
+}
+constexpr std::make_integer_sequence<int, kNumPro * kNumEpi> kFusionPairs{};
+
+template <int BM, int BN, int WM, int WN>
+void launch_igemm(const IgemmArgs& a, hipStream_t s) {
+  launch_fusion<IG_NT, BM * BN, 2>(a, s, [](auto pro, auto epi, const IgemmArgs& a, hipStream_t s) {
+    launch_igemm_t<BM, BN, WM, WN, decltype(pro)::value, decltype(epi)::value>(a, s);
+  }, kFusionPairs);
+}
 
 template <int BM, int BN, int WM, int WN, int NST = 2>
 void launch_glds(const IgemmArgs& a, hipStream_t s) {
-  if (a.pro_d != nullptr) {  // BN-backward prologue (PRO 2): plain, mode-3 or mode-4 epilogue
-    if constexpr (NST == 2) {
-      if (a.epi_mode == 3)
-        launch_glds_t<BM, BN, WM, WN, 2, 3, NST>(a, s);
-      else if (a.epi_mode == 4) {
-        // (the 256 x 256 tile with both fusions drains its DMA pipeline: not instantiated;
-        // the igemm binding rejects that combination before any launch)
-        if constexpr (BM * BN <= 256 * 128) {
-          if (a.stats2 != nullptr)
-            launch_glds_t<BM, BN, WM, WN, 2, 5, NST>(a, s);
-          else
-            launch_glds_t<BM, BN, WM, WN, 2, 4, NST>(a, s);
-        } else {
-          fprintf(stderr, "igemm: BN-backward prologue + mode-4 epilogue on a 256x256 tile\n");
-          abort();
-        }
-      } else
-        launch_glds_t<BM, BN, WM, WN, 2, 0, NST>(a, s);
-    } else {
-      fprintf(stderr, "igemm: 3-stage LDS-DMA variant with the BN-backward prologue\n");
-      abort();
-    }
-    return;
-  }
-  if (a.pro_out != nullptr) {  // block-output prologue: 2 stages, plain epilogue (host-checked)
-    if constexpr (NST == 2) {
-      launch_glds_t<BM, BN, WM, WN, 3, 0, NST>(a, s);
-    } else {
-      fprintf(stderr, "igemm: 3-stage LDS-DMA variant with the block-output prologue\n");
-      abort();
-    }
-    return;
-  }
-  if (a.pro_sc != nullptr) {
-    if constexpr (NST <= 2) {  // the 3-stage tiles leave no LDS for the prologue table
-      switch (a.epi_mode) {
-        case 1: launch_glds_t<BM, BN, WM, WN, 1, 1, NST>(a, s); break;
-        case 2: launch_glds_t<BM, BN, WM, WN, 1, 2, NST>(a, s); break;
-        case 3: launch_glds_t<BM, BN, WM, WN, 1, 3, NST>(a, s); break;
-        default: launch_glds_t<BM, BN, WM, WN, 1, 0, NST>(a, s); break;
-      }
-    } else {
-      fprintf(stderr, "igemm: 3-stage LDS-DMA variant with a prologue\n");
-      abort();  // igemm_variant_ok rejects this
-    }
-    return;
-  }
-  switch (a.epi_mode) {
-    case 1: launch_glds_t<BM, BN, WM, WN, 0, 1, NST>(a, s); break;
-    case 2: launch_glds_t<BM, BN, WM, WN, 0, 2, NST>(a, s); break;
-    case 3: launch_glds_t<BM, BN, WM, WN, 0, 3, NST>(a, s); break;
-    case 4:
-      if (a.stats2 != nullptr)
-        launch_glds_t<BM, BN, WM, WN, 0, 5, NST>(a, s);
-      else
-        launch_glds_t<BM, BN, WM, WN, 0, 4, NST>(a, s);
-      break;
-    default: launch_glds_t<BM, BN, WM, WN, 0, 0, NST>(a, s); break;
-  }
+  launch_fusion<IG_GLDS, BM * BN, NST>(a, s, [](auto pro, auto epi, const IgemmArgs& a, hipStream_t s) {
+    launch_glds_t<BM, BN, WM, WN, decltype(pro)::value, decltype(epi)::value, NST>(a, s);
+  }, kFusionPairs);
 }
 
-// compile-time fusion modes (prologue x epilogue), so each launch carries only its own work
-template <int BM, int BN, int WM, int WN>
-void launch_igemm(const IgemmArgs& a, hipStream_t s) {
-  if (a.pro_d != nullptr) {  // BN-backward prologue: plain, mode-3 or mode-4 epilogue
-    if (a.epi_mode == 3)
-      launch_igemm_t<BM, BN, WM, WN, 2, 3>(a, s);
-    else if (a.epi_mode == 4 && a.stats2 != nullptr)
-      launch_igemm_t<BM, BN, WM, WN, 2, 5>(a, s);
-    else if (a.epi_mode == 4)
-      launch_igemm_t<BM, BN, WM, WN, 2, 4>(a, s);
-    else
-      launch_igemm_t<BM, BN, WM, WN, 2, 0>(a, s);
-    return;
-  }
-  if (a.pro_sc != nullptr) {
-    switch (a.epi_mode) {
-      case 1: launch_igemm_t<BM, BN, WM, WN, 1, 1>(a, s); break;
-      case 2: launch_igemm_t<BM, BN, WM, WN, 1, 2>(a, s); break;
-      case 3: launch_igemm_t<BM, BN, WM, WN, 1, 3>(a, s); break;
-      default: launch_igemm_t<BM, BN, WM, WN, 1, 0>(a, s); break;
-    }
-    return;
-  }
-  switch (a.epi_mode) {
-    case 1: launch_igemm_t<BM, BN, WM, WN, 0, 1>(a, s); break;
-    case 2: launch_igemm_t<BM, BN, WM, WN, 0, 2>(a, s); break;
-    case 3: launch_igemm_t<BM, BN, WM, WN, 0, 3>(a, s); break;
-    case 4:
-      if (a.stats2 != nullptr)
-        launch_igemm_t<BM, BN, WM, WN, 0, 5>(a, s);
-      else
-        launch_igemm_t<BM, BN, WM, WN, 0, 4>(a, s);
-      break;
-    default: launch_igemm_t<BM, BN, WM, WN, 0, 0>(a, s); break;
-  }
+template <int BN, int WM, int WN>
+void launch_patch(const IgemmArgs& a, hipStream_t s) {
+  launch_fusion<IG_PATCH, 256 * BN, 2>(a, s, [](auto pro, auto epi, const IgemmArgs& a, hipStream_t s) {
+    launch_patch_t<BN, WM, WN, decltype(epi)::value, decltype(pro)::value>(a, s);
+  }, kFusionPairs);
 }
 
 template <int BCO, int BKK, int WM, int WN, bool DEEP = false>
@@ -2839,62 +2775,143 @@ void launch_wgrad_glds(const WgradArgs& a0, hipStream_t s) {
   HIP_CHECK_LAUNCH();
 }
 
-// tile variants: {BM, BN}
-// wide-N / wide-K tiles (5, 6 and wgrad 4, 5) cover a whole small output dimension in one tile,
-// so the other operand is streamed from HBM once instead of N/BN (K/BKK) times
-// variants >= IG_GLDS0 are the LDS-DMA kernel (igemm_glds): no prologue, C % 64 == 0
-constexpr int IG_VARIANTS[][2] = {{128, 128}, {256, 64}, {128, 64}, {64, 128}, {64, 64},
-                                  {128, 256}, {64, 256},
-                                  {256, 256}, {256, 128}, {256, 64}, {128, 128}, {128, 256},
-                                  {256, 128}, {128, 128}, {128, 256},
-                                  {256, 64}, {256, 128},
-                                  {256, 64}, {128, 256}, {256, 128},
-                                  {128, 256}, {256, 128}};
-constexpr int IG_GLDS0 = 7;   // LDS-DMA kernel from here on
-constexpr int IG_GLDS3 = 12;  // ... with three LDS stages (no BN-apply prologue)
-constexpr int IG_PATCH0 = 15;  // 3x3 stride-1 kernel with an LDS-resident input patch
-constexpr int IG_GLDS8W = 17;  // 2-stage LDS-DMA, 256 x 64 tile on 8 waves (memory-bound 1x1)
-// 18, 19: 2-stage LDS-DMA, one wave column (WN = 1): the BN-apply prologue runs on the A
-// fragments in registers (the short-K 1x1 expansion convs, conv3 of a bottleneck)
-// 20, 21: single-stage LDS-DMA tiles, 2 blocks per CU (short-K 1x1 convs: one block's loads and
-// epilogue under the other's MFMAs instead of a second LDS stage); BN-apply prologue only
-constexpr int IG_GLDS1 = 20;
-// variants >= WG_GLDS0 are the LDS-DMA kernel (wgrad_glds): no prologues, C % 64 == 0
-// {BCO, BKK, target resident blocks}: the split-M count is chosen to fill the chip with about
-// that many blocks; every split costs an fp32 N x K slab written here and re-read by the
-// reduction, so the LDS-DMA variants (1-2 blocks per CU) aim at 256-512 instead of 768
-constexpr int WG_VARIANTS[][3] = {{128, 128, 768}, {64, 128, 768}, {128, 64, 768}, {64, 64, 768},
-                                  {64, 256, 768},  {256, 64, 768},  {128, 128, 512},
-                                  {256, 128, 256}, {128, 256, 256}, {256, 256, 256},
-                                  {64, 256, 512},  {128, 128, 256}, {64, 256, 256},
-                                  {128, 64, 512},  {128, 128, 256}, {64, 128, 512},
-                                  {256, 128, 256}, {64, 64, 256},
-                                  {64, 128, 768}, {128, 64, 768},
-                                  {256, 256, 256}, {256, 128, 256}, {128, 256, 256},
-                                  {256, 256, 256},
-                                  {256, 256, 256}, {256, 128, 256}, {128, 128, 512},
-                                  {256, 256, 256}};
-constexpr int WG_GLDS0 = 6;
-constexpr int WG_PATCH0 = 17;  // wgrad_patch (3x3 stride-1, all taps from one input patch)
-// wgrad_tn with loads two steps ahead (DEEP): the 64 x 128 / 128 x 64 tiles gain 10-17 % on the
-// 3x3 / 1x1 weight gradients (tools/wgrad_probe.py); the 128 x 128 and 256 x 64 DEEP tiles spill
-// at the 256-VGPR cap of two blocks per CU and lose (not instantiated)
-constexpr int WG_DEEP0 = 18;
-// 20-22: wgrad_pipe (32-row steps, 4-5 LDS stages with all but one in flight), no prologues
-constexpr int WG_PIPE0 = 20;
-// 23: wgrad_glds 256 x 256 (8 waves) on v_mfma_f32_32x32x16_bf16 (as 9): half the MFMA and
-// ~17 % fewer VALU instructions, 1-4 % faster on the layer3 / layer4 3x3 weight gradients; the
-// other 32x32x16 tiles and the ping-pong kernel were measured and removed (r4 optimisation log)
-constexpr int WG_GLDS32 = 23;
-// 24-26: wgrad_xp (fragment reads carried across the barrier, no prologues) on 32x32x16:
-// 256 x 256 / 256 x 128 (8 waves), 128 x 128 (4 waves)
-// 27: wgrad_xp 256 x 256 on 4 waves (128 x 128 per wave, one wave per SIMD): per 64-row step the
-// 8-wave tile reads 196 KB of LDS fragments + 64 KB of DMA writes against ~2,060 MFMA clocks per
-// SIMD (LDS at parity with the MFMAs, 128 B/clk); the 128 x 128 wave tile reads 128 KB (LDS at
-// ~75 % of the MFMA time).  The 256 accumulator registers per lane live in AGPRs.  Measured
-// 15-20 % slower than 24 on every shape (one wave per SIMD: its own VALU address work and DMA
-// issue sit between its MFMAs; profiles/r6_wgrad_pmc.md); kept for the record and the sweep.
-constexpr int WG_XP0 = 24;
+void launch_wgrad_patch(const WgradArgs& a0, hipStream_t s) {
+  WgradArgs a = a0;
+  a.nCo = a.N / 64;
+  a.nKk = a.C / 64;
+  const int pp = (256 / a.OW + 2) * (a.OW + 2);
+  const size_t lds = (size_t)2 * (256 * 64 + (pp + 7) / 8 * 512) * 2 +
+                     (a.pro_sc != nullptr ? (size_t)2 * 2 * 64 * 4 : 0);
+  const dim3 grid(a.nCo * a.nKk * a.splits);
+  if (a.OW == 32) {
+    if (a.pro_sc != nullptr)
+      hipLaunchKernelGGL((wgrad_patch<true, 32>), grid, dim3(576), lds, s, a);
+    else
+      hipLaunchKernelGGL((wgrad_patch<false, 32>), grid, dim3(576), lds, s, a);
+  } else {
+    if (a.pro_sc != nullptr)
+      hipLaunchKernelGGL((wgrad_patch<true, 16>), grid, dim3(576), lds, s, a);
+    else
+      hipLaunchKernelGGL((wgrad_patch<false, 16>), grid, dim3(576), lds, s, a);
+  }
+  HIP_CHECK_LAUNCH();
+}
+
+// ---- tile variants: one row per variant; its position is its number (bench/tiles_mi355x.json and
+// the tuning keys pin numbers: append, never reorder).  A row is made from the template arguments
+// of its launcher, so the table and the instantiation cannot disagree.
+struct IgemmVariant {
+  IgFam fam;
+  int bm, bn, wm, wn, stages;
+  void (*launch)(const IgemmArgs&, hipStream_t);
+  constexpr int threads() const { return 64 * wm * wn; }
+  constexpr bool fuses(int pro, int epi) const {
+    return igemm_fusion_allowed(fam, pro, epi, bm * bn, stages);
+  }
+};
+template <int BM, int BN, int WM, int WN>
+constexpr IgemmVariant ig_nt() { return {IG_NT, BM, BN, WM, WN, 2, launch_igemm<BM, BN, WM, WN>}; }
+template <int BM, int BN, int WM, int WN, int NST = 2>
+constexpr IgemmVariant ig_glds() {
+  return {IG_GLDS, BM, BN, WM, WN, NST, launch_glds<BM, BN, WM, WN, NST>};
+}
+template <int BN, int WM, int WN>
+constexpr IgemmVariant ig_patch() { return {IG_PATCH, 256, BN, WM, WN, 2, launch_patch<BN, WM, WN>}; }
+
+constexpr IgemmVariant IG_VARIANTS[] = {
+    // 0-6: register-staged kernel (igemm_nt): every geometry and fusion.  The wide-N tiles (5, 6
+    // and wgrad 4, 5) cover a whole small output dimension in one tile, so the other operand is
+    // streamed from HBM once instead of N/BN (K/BKK) times
+    ig_nt<128, 128, 2, 2>(), ig_nt<256, 64, 4, 1>(), ig_nt<128, 64, 2, 2>(), ig_nt<64, 128, 2, 2>(),
+    ig_nt<64, 64, 2, 2>(), ig_nt<128, 256, 2, 2>(), ig_nt<64, 256, 1, 4>(),
+    // 7-11: LDS-DMA kernel (igemm_glds), two LDS stages: C % 64 == 0
+    ig_glds<256, 256, 2, 4>(), ig_glds<256, 128, 4, 2>(), ig_glds<256, 64, 4, 1>(),
+    ig_glds<128, 128, 2, 2>(), ig_glds<128, 256, 2, 4>(),
+    // 12-14: ... with three LDS stages (no prologue)
+    ig_glds<256, 128, 4, 2, 3>(), ig_glds<128, 128, 2, 2, 3>(), ig_glds<128, 256, 2, 4, 3>(),
+    // 15, 16: 3x3 stride-1 kernel with an LDS-resident input patch
+    ig_patch<64, 4, 1>(), ig_patch<128, 4, 2>(),
+    // 17: 2-stage LDS-DMA, 256 x 64 tile on 8 waves (memory-bound 1x1)
+    ig_glds<256, 64, 8, 1>(),
+    // 18, 19: 2-stage LDS-DMA, one wave column (WN = 1): the BN-apply prologue runs on the A
+    // fragments in registers (the short-K 1x1 expansion convs, conv3 of a bottleneck)
+    ig_glds<128, 256, 4, 1>(), ig_glds<256, 128, 8, 1>(),
+    // 20, 21: single-stage LDS-DMA tiles, 2 blocks per CU (short-K 1x1 convs: one block's loads
+    // and epilogue under the other's MFMAs instead of a second LDS stage); BN-apply prologue only
+    ig_glds<128, 256, 2, 2, 1>(), ig_glds<256, 128, 2, 2, 1>()};
+constexpr int kNumIgemm = (int)(sizeof(IG_VARIANTS) / sizeof(IG_VARIANTS[0]));
+
+enum WgFam { WG_TN, WG_TN_DEEP, WG_GLDS, WG_PATCH, WG_PIPE, WG_XP };
+struct WgradVariant {
+  WgFam fam;
+  int bco, bkk;
+  int target;  // resident blocks the split-M count aims at: every split costs an fp32 N x K slab
+               // written here and re-read by the reduction, so the LDS-DMA variants (1-2 blocks
+               // per CU) aim at 256-512 instead of 768
+  int rows;    // output rows per iteration (the unit of a split)
+  void (*launch)(const WgradArgs&, hipStream_t);
+  // LDS-DMA operand loads: C % 64 == 0, an X prologue only on unpadded 1x1 convolutions
+  constexpr bool lds_dma() const { return fam == WG_GLDS || fam == WG_PIPE || fam == WG_XP; }
+  constexpr bool x_pro() const { return fam != WG_PIPE && fam != WG_XP; }       // BN-apply on X
+  constexpr bool dy_pro() const { return fam == WG_TN || fam == WG_TN_DEEP; }   // BN-backward on dY
+  // the patch kernel's K tile is all 9 taps of 64 input channels
+  constexpr int k_tiles(int C, int K) const { return fam == WG_PATCH ? C / 64 : (K + bkk - 1) / bkk; }
+  constexpr int min_iters() const { return fam == WG_PATCH ? 1 : 8; }  // per split
+  // iterations over M output rows: the patch kernel runs whole 256-row iterations only
+  constexpr int iters(int M) const { return fam == WG_PATCH ? M / rows : (M + rows - 1) / rows; }
+};
+template <int BCO, int BKK, int WM, int WN, bool DEEP = false>
+constexpr WgradVariant wg_tn(int target) {
+  return {DEEP ? WG_TN_DEEP : WG_TN, BCO, BKK, target, 64, launch_wgrad<BCO, BKK, WM, WN, DEEP>};
+}
+template <int BCO, int BKK, int WM, int WN, int NST = 2, int MF = 16>
+constexpr WgradVariant wg_glds(int target) {
+  return {WG_GLDS, BCO, BKK, target, 64, launch_wgrad_glds<BCO, BKK, WM, WN, NST, MF>};
+}
+template <int BCO, int BKK, int WM, int WN, int SR, int NST>
+constexpr WgradVariant wg_pipe(int target) {
+  return {WG_PIPE, BCO, BKK, target, 64, launch_wgrad_pipe<BCO, BKK, WM, WN, SR, NST>};
+}
+template <int BCO, int BKK, int WM, int WN, int MF>
+constexpr WgradVariant wg_xp(int target) {
+  return {WG_XP, BCO, BKK, target, 64, launch_wgrad_xp<BCO, BKK, WM, WN, MF>};
+}
+
+constexpr WgradVariant WG_VARIANTS[] = {
+    // 0-5: register-staged kernel (wgrad_tn): every geometry and prologue
+    wg_tn<128, 128, 2, 2>(768), wg_tn<64, 128, 2, 2>(768), wg_tn<128, 64, 2, 2>(768),
+    wg_tn<64, 64, 2, 2>(768), wg_tn<64, 256, 2, 2>(768), wg_tn<256, 64, 2, 2>(768),
+    // 6-16: LDS-DMA kernel (wgrad_glds): the X-operand BN-apply prologue only.  4-wave tiles with
+    // 128x64 / 64x128 per wave: half the LDS fragment bytes per MFMA of a 64x64 wave tile (the
+    // 128x128 wgrad was LDS-bound between DMA writes and tr reads); 13-16 with three LDS stages
+    wg_glds<128, 128, 2, 2>(512), wg_glds<256, 128, 2, 2>(256), wg_glds<128, 256, 2, 2>(256),
+    wg_glds<256, 256, 2, 4>(256), wg_glds<64, 256, 1, 4>(512), wg_glds<128, 128, 2, 2>(256),
+    wg_glds<64, 256, 1, 4>(256), wg_glds<128, 64, 2, 2, 3>(512), wg_glds<128, 128, 2, 2, 3>(256),
+    wg_glds<64, 128, 2, 2, 3>(512), wg_glds<256, 128, 2, 2, 3>(256),
+    // 17: wgrad_patch (3x3 stride-1, all taps from one input patch, 256-row iterations)
+    {WG_PATCH, 64, 64, 256, 256, launch_wgrad_patch},
+    // 18, 19: wgrad_tn with loads two steps ahead (DEEP): the 64 x 128 / 128 x 64 tiles gain
+    // 10-17 % on the 3x3 / 1x1 weight gradients (tools/wgrad_probe.py); the 128 x 128 and
+    // 256 x 64 DEEP tiles spill at the 256-VGPR cap of two blocks per CU and lose (not instantiated)
+    wg_tn<64, 128, 2, 2, true>(768), wg_tn<128, 64, 2, 2, true>(768),
+    // 20-22: wgrad_pipe (32-row steps, 4-5 LDS stages with all but one in flight), no prologues
+    wg_pipe<256, 256, 2, 4, 32, 4>(256), wg_pipe<256, 128, 4, 2, 32, 5>(256),
+    wg_pipe<128, 256, 2, 4, 32, 5>(256),
+    // 23: wgrad_glds 256 x 256 (8 waves) on v_mfma_f32_32x32x16_bf16 (as 9): half the MFMA and
+    // ~17 % fewer VALU instructions, 1-4 % faster on the layer3 / layer4 3x3 weight gradients; the
+    // other 32x32x16 tiles and the ping-pong kernel were measured and removed (r4 optimisation log)
+    wg_glds<256, 256, 2, 4, 2, 32>(256),
+    // 24-26: wgrad_xp (fragment reads carried across the barrier, no prologues) on 32x32x16:
+    // 256 x 256 / 256 x 128 (8 waves), 128 x 128 (4 waves)
+    wg_xp<256, 256, 2, 4, 32>(256), wg_xp<256, 128, 4, 2, 32>(256), wg_xp<128, 128, 2, 2, 32>(512),
+    // 27: wgrad_xp 256 x 256 on 4 waves (128 x 128 per wave, one wave per SIMD): per 64-row step the
+    // 8-wave tile reads 196 KB of LDS fragments + 64 KB of DMA writes against ~2,060 MFMA clocks per
+    // SIMD (LDS at parity with the MFMAs, 128 B/clk); the 128 x 128 wave tile reads 128 KB (LDS at
+    // ~75 % of the MFMA time).  The 256 accumulator registers per lane live in AGPRs.  Measured
+    // 15-20 % slower than 24 on every shape (one wave per SIMD: its own VALU address work and DMA
+    // issue sit between its MFMAs; profiles/r6_wgrad_pmc.md); kept for the record and the sweep.
+    wg_xp<256, 256, 2, 2, 32>(256)};
+constexpr int kNumWgrad = (int)(sizeof(WG_VARIANTS) / sizeof(WG_VARIANTS[0]));
 
 
 // -------------------------------------------------- fused 1x1 backward: dgrad + wgrad in one pass
@@ -3435,64 +3452,66 @@ void conv_weight_transform_batch(const WtDesc* d, int n, int total_blocks, hipSt
   HIP_CHECK_LAUNCH();
 }
 
-int igemm_num_variants() { return (int)(sizeof(IG_VARIANTS) / sizeof(IG_VARIANTS[0])); }
-int igemm_variant_bm(int v) { return IG_VARIANTS[v][0]; }
-int igemm_variant_bn(int v) { return IG_VARIANTS[v][1]; }
+int igemm_num_variants() { return kNumIgemm; }
+int igemm_variant_bm(int v) { return IG_VARIANTS[v].bm; }
+int igemm_variant_bn(int v) { return IG_VARIANTS[v].bn; }
 int igemm_default_variant(int N) { return N <= 64 ? 1 : 0; }
-bool igemm_variant_glds(int v) { return v >= IG_GLDS0 && v < igemm_num_variants(); }
+bool igemm_variant_glds(int v) { return v >= 0 && v < kNumIgemm && IG_VARIANTS[v].fam != IG_NT; }
+bool igemm_variant_patch(int v) {
+  return v >= 0 && v < kNumIgemm && IG_VARIANTS[v].fam == IG_PATCH;
+}
 bool igemm_glds_ok(const ConvGeom& g, bool pro, bool bn_bwd_pro) {
   if (g.C % 64 != 0) return false;
   // the BN-apply / BN-backward prologues run on the landed tile: only valid without
   // zero-padding taps
   return !(pro || bn_bwd_pro) || (g.KH == 1 && g.KW == 1 && g.ih0 == 0 && g.iw0 == 0);
 }
-bool igemm_variant_patch(int v) { return v >= IG_PATCH0 && v < IG_GLDS8W; }
+static bool direct_out(const ConvGeom& g) {
+  return g.osh == 1 && g.osw == 1 && g.ooh == 0 && g.oow == 0 && g.OHp == g.OH && g.OWp == g.OW;
+}
 bool igemm_patch_ok(const ConvGeom& g) {
-  const bool direct = g.osh == 1 && g.osw == 1 && g.ooh == 0 && g.oow == 0 && g.OHp == g.OH &&
-                      g.OWp == g.OW;
   return g.KH == 3 && g.KW == 3 && g.ish == 1 && g.isw == 1 && g.dh == 1 && g.dw == 1 &&
          g.ih0 == -1 && g.iw0 == -1 && g.OH == g.IH && g.OW == g.IW &&
-         (g.OW == 16 || g.OW == 32) && (g.C == 64 || g.C == 128) && direct;
+         (g.OW == 16 || g.OW == 32) && (g.C == 64 || g.C == 128) && direct_out(g);
+}
+// LDS-DMA tile with the doubled A staging of PRO 2 / 3 and `words` fp32 table words per channel
+static bool glds_doubled_fits(const IgemmVariant& r, const ConvGeom& g, int words) {
+  const size_t lds = igemm_glds_pro_offset(r.bm, r.bn, r.threads(), g.C > 64 ? 2 : 1, 2) +
+                     (size_t)4 * words * g.C;
+  return lds <= 160 * 1024;
 }
 // block-output prologue (PRO 3): 2-stage LDS-DMA tiles whose doubled A staging fits the LDS,
 // on 1x1 / stride-1 / unpadded / direct-output convolutions (A row m = output row m)
 bool igemm_dual_ok(int v, const ConvGeom& g) {
-  if (!((v >= IG_GLDS0 && v < IG_GLDS3) || (v >= IG_GLDS8W && v < IG_GLDS1)) ||
-      !igemm_glds_ok(g, true, false))
-    return false;
-  const bool direct = g.osh == 1 && g.osw == 1 && g.ooh == 0 && g.oow == 0 && g.OHp == g.OH &&
-                      g.OWp == g.OW;
-  if (!(direct && g.ish == 1 && g.isw == 1 && g.OH == g.IH && g.OW == g.IW)) return false;
-  const int BM = IG_VARIANTS[v][0], BN = IG_VARIANTS[v][1];
-  if ((g.Nb * g.OH * g.OW) % BM) return false;  // whole tiles: the kernel counts its stores
-  const int NT = 512;  // upper bound of the tiles' threads (only sizes the stats scratch)
-  const size_t lds = igemm_glds_pro_offset(BM, BN, NT, g.C > 64 ? 2 : 1, 2) + (size_t)16 * g.C;
-  return lds <= 160 * 1024;
+  if (v < 0 || v >= kNumIgemm) return false;
+  const IgemmVariant& r = IG_VARIANTS[v];
+  if (!r.fuses(3, 0) || !igemm_glds_ok(g, true, false)) return false;
+  if (!(direct_out(g) && g.ish == 1 && g.isw == 1 && g.OH == g.IH && g.OW == g.IW)) return false;
+  if ((g.Nb * g.OH * g.OW) % r.bm) return false;  // whole tiles: the kernel counts its stores
+  return glds_doubled_fits(r, g, 4);
 }
 
-
-bool igemm_variant_is_patch(int v) { return v >= IG_PATCH0 && v < IG_GLDS8W; }
-
-bool igemm_variant_ok(int v, const ConvGeom& g, bool pro, bool bn_bwd_pro) {
-  if (v < 0 || v >= igemm_num_variants()) return false;
-  if (v < IG_GLDS0) return true;  // register-staged kernel: every geometry and fusion
-  // patch kernel: BN-apply prologue, or the BN-backward one while its second operand fits the
-  // per-thread register stage (kPatchBnbChunks chunks of the patch per thread)
-  if (v >= IG_PATCH0 && v < IG_GLDS8W) {
-    if (!igemm_patch_ok(g)) return false;
-    if (!bn_bwd_pro) return true;
-    const int NT = v == IG_PATCH0 ? 256 : 512;  // launch_patch<64, 4, 1> / <128, 4, 2>
-    const int TR = 256 / g.OW, PP = (TR + 2) * (g.OW + 2);
-    return (PP * (g.C / 8) + NT - 1) / NT <= kPatchBnbChunks;
+bool igemm_variant_ok(int v, const ConvGeom& g, bool pro, bool bn_bwd_pro, int epi_mode) {
+  if (v < 0 || v >= kNumIgemm) return false;
+  const IgemmVariant& r = IG_VARIANTS[v];
+  // the epilogue matters where it depends on the tile: the LDS-DMA kernel's BN-backward prologue
+  // with mode 4.  (The holes that do not depend on the tile are fusion rules of the bindings.)
+  const bool bwd4 = bn_bwd_pro && (epi_mode & 255) == 4 && r.fam == IG_GLDS;
+  if (!r.fuses(igemm_pro_code(pro, bn_bwd_pro, false), bwd4 ? 4 : 0)) return false;
+  switch (r.fam) {
+    case IG_NT: return true;  // every geometry
+    case IG_PATCH: {
+      if (!igemm_patch_ok(g)) return false;
+      if (!bn_bwd_pro) return true;
+      // BN-backward prologue: its second operand must fit the per-thread register stage
+      // (kPatchBnbChunks chunks of the patch per thread)
+      const int TR = 256 / g.OW, PP = (TR + 2) * (g.OW + 2), NT = r.threads();
+      return (PP * (g.C / 8) + NT - 1) / NT <= kPatchBnbChunks;
+    }
+    case IG_GLDS:  // PRO 2 stages dY and x: doubled A staging + a 3 x C table must fit
+      return (!bn_bwd_pro || glds_doubled_fits(r, g, 3)) && igemm_glds_ok(g, pro, bn_bwd_pro);
   }
-  if (v >= IG_GLDS1) return !bn_bwd_pro && igemm_glds_ok(g, pro, false);
-  if (v >= IG_GLDS3 && v < IG_PATCH0 && (pro || bn_bwd_pro)) return false;
-  if (bn_bwd_pro) {  // PRO 2 stages dY and x: doubled A staging + a 3 x C table must fit
-    const int BM = IG_VARIANTS[v][0], BN = IG_VARIANTS[v][1];
-    const size_t lds = igemm_glds_pro_offset(BM, BN, 512, g.C > 64 ? 2 : 1, 2) + (size_t)12 * g.C;
-    if (lds > 160 * 1024) return false;
-  }
-  return igemm_glds_ok(g, pro, bn_bwd_pro);
+  return false;
 }
 int igemm_block_m(int N) { return igemm_variant_bm(igemm_default_variant(N)); }
 
@@ -3507,8 +3526,7 @@ void conv_igemm_nt(const ConvGeom& g, const uint16_t* A, size_t a_elems, const u
   a.ish = g.ish; a.isw = g.isw; a.dh = g.dh; a.dw = g.dw; a.ih0 = g.ih0; a.iw0 = g.iw0;
   a.OHp = g.OHp; a.OWp = g.OWp; a.osh = g.osh; a.osw = g.osw; a.ooh = g.ooh; a.oow = g.oow;
   a.ldo = g.ldo;
-  a.direct_out = (g.osh == 1 && g.osw == 1 && g.ooh == 0 && g.oow == 0 && g.OHp == g.OH &&
-                  g.OWp == g.OW) ? 1 : 0;
+  a.direct_out = direct_out(g) ? 1 : 0;
   a.a_bytes = (uint32_t)(a_elems * 2);
   a.b_bytes = (uint32_t)((size_t)a.N * a.K * 2);
   a.pro_sc = f.pro_sc; a.pro_sh = f.pro_sh; a.pro_seg_rows = f.pro_seg_rows > 0 ? f.pro_seg_rows : a.M;
@@ -3524,61 +3542,38 @@ void conv_igemm_nt(const ConvGeom& g, const uint16_t* A, size_t a_elems, const u
   const bool dual = a.pro_out != nullptr && a.pro_d == nullptr;  // (with pro_d: materialised
                                                                  //  BN-backward operand, patch)
   if (dual ? !igemm_dual_ok(variant, g)
-           : !igemm_variant_ok(variant, g, a.pro_sc != nullptr, a.pro_d != nullptr)) {
-    fprintf(stderr, "igemm: LDS-DMA variant %d: unsupported geometry / prologue\n", variant);
+           : !igemm_variant_ok(variant, g, a.pro_sc != nullptr, a.pro_d != nullptr, a.epi_mode)) {
+    fprintf(stderr, "igemm: variant %d: unsupported geometry / fusion\n", variant);
     abort();  // the bindings reject this; never silently change BM (stats layout)
   }
-  switch (variant) {
-    case 7: launch_glds<256, 256, 2, 4>(a, s); break;
-    case 8: launch_glds<256, 128, 4, 2>(a, s); break;
-    case 9: launch_glds<256, 64, 4, 1>(a, s); break;
-    case 10: launch_glds<128, 128, 2, 2>(a, s); break;
-    case 11: launch_glds<128, 256, 2, 4>(a, s); break;
-    case 12: launch_glds<256, 128, 4, 2, 3>(a, s); break;
-    case 13: launch_glds<128, 128, 2, 2, 3>(a, s); break;
-    case 14: launch_glds<128, 256, 2, 4, 3>(a, s); break;
-    case 15: launch_patch<64, 4, 1>(a, s); break;
-    case 16: launch_patch<128, 4, 2>(a, s); break;
-    case 17: launch_glds<256, 64, 8, 1>(a, s); break;
-    case 18: launch_glds<128, 256, 4, 1>(a, s); break;
-    case 19: launch_glds<256, 128, 8, 1>(a, s); break;
-    case 20: launch_glds<128, 256, 2, 2, 1>(a, s); break;
-    case 21: launch_glds<256, 128, 2, 2, 1>(a, s); break;
-    case 0: launch_igemm<128, 128, 2, 2>(a, s); break;
-    case 1: launch_igemm<256, 64, 4, 1>(a, s); break;
-    case 2: launch_igemm<128, 64, 2, 2>(a, s); break;
-    case 3: launch_igemm<64, 128, 2, 2>(a, s); break;
-    case 5: launch_igemm<128, 256, 2, 2>(a, s); break;
-    case 6: launch_igemm<64, 256, 1, 4>(a, s); break;
-    default: launch_igemm<64, 64, 2, 2>(a, s); break;
-  }
+  IG_VARIANTS[variant].launch(a, s);
 }
 
 
-int wgrad_num_variants() { return (int)(sizeof(WG_VARIANTS) / sizeof(WG_VARIANTS[0])); }
+int wgrad_num_variants() { return kNumWgrad; }
 int wgrad_xlin(int mode) { return xlin_mode(mode); }
 int wgrad_default_variant(int N) { return N <= 64 ? 1 : 0; }
-bool wgrad_variant_glds(int v) { return (v >= WG_GLDS0 && v < WG_PATCH0) || v >= WG_PIPE0; }
-int wgrad_variant_area(int v) { return WG_VARIANTS[v][0] * WG_VARIANTS[v][1]; }
+bool wgrad_variant_glds(int v) { return v >= 0 && v < kNumWgrad && WG_VARIANTS[v].lds_dma(); }
+int wgrad_variant_area(int v) { return WG_VARIANTS[v].bco * WG_VARIANTS[v].bkk; }
 bool wgrad_variant_ok(int v, const ConvGeom& g, bool pro, bool dy_pro) {
-  if (v < 0 || v >= wgrad_num_variants()) return false;
-  if (v == WG_PATCH0) return !dy_pro && g.N % 64 == 0 && igemm_patch_ok(g);
-  if (v == WG_GLDS32) return !dy_pro && igemm_glds_ok(g, pro, false);
-  if (v >= WG_PIPE0) return !dy_pro && !pro && igemm_glds_ok(g, false, false);
-  if (v >= WG_DEEP0) return true;  // register-staged: every prologue
-  // wgrad_glds has the X-operand BN-apply prologue only (no dY BN-backward prologue)
-  return v < WG_GLDS0 || (!dy_pro && igemm_glds_ok(g, pro, false));
+  if (v < 0 || v >= kNumWgrad) return false;
+  const WgradVariant& r = WG_VARIANTS[v];
+  if ((pro && !r.x_pro()) || (dy_pro && !r.dy_pro())) return false;
+  if (r.fam == WG_PATCH) return g.N % 64 == 0 && igemm_patch_ok(g);
+  return !r.lds_dma() || igemm_glds_ok(g, pro, false);
+}
+
+int wgrad_tiles(const ConvGeom& g, int variant) {
+  if (variant < 0 || variant >= kNumWgrad) variant = wgrad_default_variant(g.N);
+  const WgradVariant& r = WG_VARIANTS[variant];
+  return ((g.N + r.bco - 1) / r.bco) * r.k_tiles(g.C, g.KH * g.KW * g.C);
 }
 
 int wgrad_splits(const ConvGeom& g, int variant) {
-  if (variant < 0 || variant >= wgrad_num_variants()) variant = wgrad_default_variant(g.N);
-  const int bco = WG_VARIANTS[variant][0], bkk = WG_VARIANTS[variant][1];
-  const int M = g.Nb * g.OH * g.OW;
-  const int K = g.KH * g.KW * g.C;
-  const bool patch = variant == WG_PATCH0;
-  // the patch kernel's K tile is all 9 taps of 64 input channels; its M unit is 256 rows
-  const int tiles = ((g.N + bco - 1) / bco) * (patch ? g.C / 64 : (K + bkk - 1) / bkk);
-  const int iters = patch ? M / 256 : (M + 63) / 64;
+  if (variant < 0 || variant >= kNumWgrad) variant = wgrad_default_variant(g.N);
+  const WgradVariant& r = WG_VARIANTS[variant];
+  const int tiles = wgrad_tiles(g, variant);
+  const int iters = r.iters(g.Nb * g.OH * g.OW);
   // The weight gradients run on their own stream beside the dgrad / BatchNorm chain, so they
   // need not fill the chip alone, and every split costs an fp32 N x K slab written here and
   // re-read by the split reduction: the step is fastest at ~60-80 % of the targets tuned for a
@@ -3589,22 +3584,38 @@ int wgrad_splits(const ConvGeom& g, int variant) {
     const int v = e ? atoi(e) : 80;  // end of round 3: 80 beat 60 in 5 of 5 A/B rounds
     return v > 0 ? v : 100;
   }();
-  const int target =
-      std::max(1, WG_VARIANTS[variant][2] * pct / 100);
-  int splits = (target + tiles - 1) / tiles;
-  int max_splits = patch ? iters : iters / 8;
-  if (max_splits < 1) max_splits = 1;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  return splits;
+  const int target = std::max(1, r.target * pct / 100);
+  const int splits = (target + tiles - 1) / tiles;
+  return std::max(1, std::min(splits, iters / r.min_iters()));
 }
 
-int wgrad_tiles(const ConvGeom& g, int variant) {
-  if (variant < 0 || variant >= wgrad_num_variants()) variant = wgrad_default_variant(g.N);
-  const int K = g.KH * g.KW * g.C;
-  if (variant == WG_PATCH0) return (g.N / 64) * (g.C / 64);
-  const int bco = WG_VARIANTS[variant][0], bkk = WG_VARIANTS[variant][1];
-  return ((g.N + bco - 1) / bco) * ((K + bkk - 1) / bkk);
+// ---- split reduction over [splits][4 * n4] fp32 slabs: one column-parallel kernel where it
+// applies, else groups of 16 slabs pre-summed in place, then the float4 sum into the output
+struct SlabsLeft { int count, stride; };  // slabs still to be summed, `stride` slabs apart
+static SlabsLeft reduce_slabs_l1(float* partial, int splits, size_t n4, hipStream_t s) {
+  constexpr int GROUP = 16;
+  if (splits <= 2 * GROUP) return {splits, 1};
+  const int G = (splits + GROUP - 1) / GROUP;
+  const int bx = (int)std::min<size_t>((n4 + 255) / 256, 1024);
+  hipLaunchKernelGGL(wgrad_reduce_l1, dim3(bx, G), dim3(256), 0, s, (float4*)partial, splits,
+                     GROUP, n4);
+  HIP_CHECK_LAUNCH();
+  return {G, GROUP};
+}
+// vec4: the slab size is a multiple of 4 floats (else only the final sum runs, on the whole float4s)
+static void reduce_slabs(float* partial, int splits, float* out, size_t n4, float beta, bool vec4,
+                         hipStream_t s) {
+  if (vec4 && reduce_cols_ok(n4, splits)) {
+    hipLaunchKernelGGL(wgrad_reduce_cols, dim3((unsigned)((n4 + RC_COLS - 1) / RC_COLS)),
+                       dim3(256), 0, s, (const float4*)partial, (float4*)out, splits, n4, beta);
+    HIP_CHECK_LAUNCH();
+    return;
+  }
+  const SlabsLeft left = vec4 ? reduce_slabs_l1(partial, splits, n4, s) : SlabsLeft{splits, 1};
+  const int blocks = (int)std::min<size_t>((n4 + 255) / 256, 8192);
+  hipLaunchKernelGGL(wgrad_reduce_vec4, dim3(blocks), dim3(256), 0, s, (const float4*)partial,
+                     (float4*)out, left.count, left.stride, n4, beta);
+  HIP_CHECK_LAUNCH();
 }
 
 void conv_wgrad(const ConvGeom& g, const uint16_t* dY, const uint16_t* X, size_t x_elems,
@@ -3618,7 +3629,9 @@ void conv_wgrad(const ConvGeom& g, const uint16_t* dY, const uint16_t* X, size_t
   a.ish = g.ish; a.isw = g.isw; a.dh = g.dh; a.dw = g.dw; a.ih0 = g.ih0; a.iw0 = g.iw0;
   a.dy_bytes = (uint32_t)((size_t)a.M * a.N * 2);
   a.x_bytes = (uint32_t)(x_elems * 2);
-  const int iters = variant == WG_PATCH0 ? a.M / 256 : (a.M + 63) / 64;
+  if (variant < 0 || variant >= kNumWgrad) variant = wgrad_default_variant(g.N);
+  const WgradVariant& r = WG_VARIANTS[variant];
+  const int iters = r.iters(a.M);
   a.splits = splits;
   a.iters_per_split = (iters + splits - 1) / splits;
   a.pro_sc = f.pro_sc; a.pro_sh = f.pro_sh;
@@ -3639,113 +3652,39 @@ void conv_wgrad(const ConvGeom& g, const uint16_t* dY, const uint16_t* X, size_t
     return 0;
   }();
   if (slab_exp == 2) a.slab_stride = 0;
-  if (variant < 0 || variant >= wgrad_num_variants()) variant = wgrad_default_variant(g.N);
   if (!wgrad_variant_ok(variant, g, a.pro_sc != nullptr, a.dY2 != nullptr)) {
-    fprintf(stderr, "wgrad: LDS-DMA variant %d: unsupported geometry / prologue\n", variant);
+    fprintf(stderr, "wgrad: variant %d: unsupported geometry / prologue\n", variant);
     abort();  // the bindings reject this
   }
-  switch (variant) {
-    // 4-wave tiles with 128x64 / 64x128 per wave: half the LDS fragment bytes per MFMA of a
-    // 64x64 wave tile (the 128x128 wgrad was LDS-bound between DMA writes and tr reads)
-    case 6: launch_wgrad_glds<128, 128, 2, 2>(a, s); break;
-    case 7: launch_wgrad_glds<256, 128, 2, 2>(a, s); break;
-    case 8: launch_wgrad_glds<128, 256, 2, 2>(a, s); break;
-    case 9: launch_wgrad_glds<256, 256, 2, 4>(a, s); break;
-    case 10: launch_wgrad_glds<64, 256, 1, 4>(a, s); break;
-    case 11: launch_wgrad_glds<128, 128, 2, 2>(a, s); break;
-    case 12: launch_wgrad_glds<64, 256, 1, 4>(a, s); break;
-    case 13: launch_wgrad_glds<128, 64, 2, 2, 3>(a, s); break;
-    case 14: launch_wgrad_glds<128, 128, 2, 2, 3>(a, s); break;
-    case 15: launch_wgrad_glds<64, 128, 2, 2, 3>(a, s); break;
-    case 16: launch_wgrad_glds<256, 128, 2, 2, 3>(a, s); break;
-    case 17: {
-      a.nCo = a.N / 64;
-      a.nKk = a.C / 64;
-      const int pp = (256 / a.OW + 2) * (a.OW + 2);
-      const size_t lds = (size_t)2 * (256 * 64 + (pp + 7) / 8 * 512) * 2 +
-                         (a.pro_sc != nullptr ? (size_t)2 * 2 * 64 * 4 : 0);
-      const dim3 grid(a.nCo * a.nKk * a.splits);
-      if (a.OW == 32) {
-        if (a.pro_sc != nullptr)
-          hipLaunchKernelGGL((wgrad_patch<true, 32>), grid, dim3(576), lds, s, a);
-        else
-          hipLaunchKernelGGL((wgrad_patch<false, 32>), grid, dim3(576), lds, s, a);
-      } else {
-        if (a.pro_sc != nullptr)
-          hipLaunchKernelGGL((wgrad_patch<true, 16>), grid, dim3(576), lds, s, a);
-        else
-          hipLaunchKernelGGL((wgrad_patch<false, 16>), grid, dim3(576), lds, s, a);
-      }
-      HIP_CHECK_LAUNCH();
-      break;
-    }
-    case 18: launch_wgrad<64, 128, 2, 2, true>(a, s); break;
-    case 19: launch_wgrad<128, 64, 2, 2, true>(a, s); break;
-    case 20: launch_wgrad_pipe<256, 256, 2, 4, 32, 4>(a, s); break;
-    case 21: launch_wgrad_pipe<256, 128, 4, 2, 32, 5>(a, s); break;
-    case 22: launch_wgrad_pipe<128, 256, 2, 4, 32, 5>(a, s); break;
-    case 23: launch_wgrad_glds<256, 256, 2, 4, 2, 32>(a, s); break;
-    case 24: launch_wgrad_xp<256, 256, 2, 4, 32>(a, s); break;
-    case 25: launch_wgrad_xp<256, 128, 4, 2, 32>(a, s); break;
-    case 26: launch_wgrad_xp<128, 128, 2, 2, 32>(a, s); break;
-    case 27: launch_wgrad_xp<256, 256, 2, 2, 32>(a, s); break;
-    case 0: launch_wgrad<128, 128, 2, 2>(a, s); break;
-    case 1: launch_wgrad<64, 128, 2, 2>(a, s); break;
-    case 2: launch_wgrad<128, 64, 2, 2>(a, s); break;
-    case 4: launch_wgrad<64, 256, 2, 2>(a, s); break;
-    case 5: launch_wgrad<256, 64, 2, 2>(a, s); break;
-    default: launch_wgrad<64, 64, 2, 2>(a, s); break;
-  }
+  r.launch(a, s);
   const int K = a.K;
   // one split writing its slab straight into the output (the caller passed partial == out): the
   // slab IS the [N][K] fp32 gradient, no reduction launch
   if (splits == 1 && partial == out && Creal == g.C && beta == 0.f) return;
   if (slab_exp != 0) return;
   const size_t n4 = (size_t)a.N * K / 4;
-  int sstride = 1, count = splits;
-  constexpr int GROUP = 16;
-  if (Creal == g.C && (a.N * K) % 4 == 0 && reduce_cols_ok(n4, splits)) {
-    hipLaunchKernelGGL(wgrad_reduce_cols, dim3((unsigned)((n4 + RC_COLS - 1) / RC_COLS)),
-                       dim3(256), 0, s, (const float4*)partial, (float4*)out, splits, n4, beta);
-    HIP_CHECK_LAUNCH();
+  const bool vec4 = (a.N * K) % 4 == 0;
+  if (Creal == g.C) {
+    reduce_slabs(partial, splits, out, n4, beta, vec4, s);
     return;
   }
-  if (splits > 2 * GROUP && (a.N * K) % 4 == 0) {
-    const int G = (splits + GROUP - 1) / GROUP;
-    int bx = (int)((n4 + 255) / 256);
-    if (bx > 1024) bx = 1024;
-    hipLaunchKernelGGL(wgrad_reduce_l1, dim3(bx, G), dim3(256), 0, s, (float4*)partial, splits,
-                       GROUP, n4);
-    HIP_CHECK_LAUNCH();
-    sstride = GROUP;
-    count = G;
-  }
-  if (Creal == g.C) {
-    int blocks = (int)((n4 + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(wgrad_reduce_vec4, dim3(blocks), dim3(256), 0, s, (const float4*)partial,
-                       (float4*)out, count, sstride, n4, beta);
-  } else if (count > 1 && (a.N * K) % 4 == 0) {
-    // channel-padded input (the stem: 3 image channels gathered as 8): the slabs are summed
-    // with float4 loads into slab 0 in place (each element owned by one thread), then slab 0
-    // is compacted to the Creal channels — the scalar strided reduction over many slabs was
-    // 46 µs at the very end of the backward
-    int blocks = (int)((n4 + 255) / 256);
-    if (blocks > 8192) blocks = 8192;
+  // channel-padded input (the stem: 3 image channels gathered as 8)
+  const SlabsLeft left = vec4 ? reduce_slabs_l1(partial, splits, n4, s) : SlabsLeft{splits, 1};
+  const size_t total = (size_t)a.N * (K / g.C) * Creal;
+  const int cb = (int)std::min<size_t>((total + 255) / 256, 4096);
+  if (left.count > 1 && vec4) {
+    // the slabs are summed with float4 loads into slab 0 in place (each element owned by one
+    // thread), then slab 0 is compacted to the Creal channels — the scalar strided reduction
+    // over many slabs was 46 µs at the very end of the backward
+    const int blocks = (int)std::min<size_t>((n4 + 255) / 256, 8192);
     hipLaunchKernelGGL(wgrad_reduce_vec4_inplace, dim3(blocks), dim3(256), 0, s,
-                       (float4*)partial, count, sstride, n4);
+                       (float4*)partial, left.count, left.stride, n4);
     HIP_CHECK_LAUNCH();
-    const size_t total = (size_t)a.N * (K / g.C) * Creal;
-    int cb = (int)((total + 255) / 256);
-    if (cb > 4096) cb = 4096;
     hipLaunchKernelGGL(wgrad_reduce, dim3(cb), dim3(256), 0, s, partial, out, 1, 1, a.N, K, g.C,
                        Creal, beta);
   } else {
-    const size_t total = (size_t)a.N * (K / g.C) * Creal;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(wgrad_reduce, dim3(blocks), dim3(256), 0, s, partial, out, count, sstride,
-                       a.N, K, g.C, Creal, beta);
+    hipLaunchKernelGGL(wgrad_reduce, dim3(cb), dim3(256), 0, s, partial, out, left.count,
+                       left.stride, a.N, K, g.C, Creal, beta);
   }
   HIP_CHECK_LAUNCH();
 }
@@ -3849,32 +3788,10 @@ void conv1x1_bwd_dual_s2(const uint16_t* G, const uint16_t* A3, const float* coe
   HIP_CHECK_LAUNCH();
 }
 
-// out[n4] (+)= Σ_s slabs (the separate split reduction of conv_wgrad, for producers that write
+// out[n] (+)= Σ_s slabs (the split reduction of conv_wgrad, for producers that write
 // [splits][N*K] fp32 slabs themselves)
 void wgrad_reduce_slabs(float* partial, int splits, float* out, size_t n, float beta,
                         hipStream_t s) {
-  const size_t n4 = n / 4;
-  int sstride = 1, count = splits;
-  constexpr int GROUP = 16;
-  if (reduce_cols_ok(n4, splits)) {
-    hipLaunchKernelGGL(wgrad_reduce_cols, dim3((unsigned)((n4 + RC_COLS - 1) / RC_COLS)),
-                       dim3(256), 0, s, (const float4*)partial, (float4*)out, splits, n4, beta);
-    HIP_CHECK_LAUNCH();
-    return;
-  }
-  if (splits > 2 * GROUP) {
-    const int G = (splits + GROUP - 1) / GROUP;
-    int bx = (int)((n4 + 255) / 256);
-    if (bx > 1024) bx = 1024;
-    hipLaunchKernelGGL(wgrad_reduce_l1, dim3(bx, G), dim3(256), 0, s, (float4*)partial, splits,
-                       GROUP, n4);
-    HIP_CHECK_LAUNCH();
-    sstride = GROUP;
-    count = G;
-  }
-  int blocks = (int)((n4 + 255) / 256);
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(wgrad_reduce_vec4, dim3(blocks), dim3(256), 0, s, (const float4*)partial,
-                     (float4*)out, count, sstride, n4, beta);
-  HIP_CHECK_LAUNCH();
+  reduce_slabs(partial, splits, out, n / 4, beta, true, s);
 }
+

@@ -57,15 +57,19 @@ int igemm_num_variants();
 int igemm_variant_bm(int v);
 int igemm_variant_bn(int v);
 int igemm_default_variant(int N);
-bool igemm_variant_glds(int v);  // LDS-DMA variant (see igemm_glds_ok)
-bool igemm_glds_ok(const ConvGeom& g, bool pro, bool bn_bwd_pro);
-// can tile variant v run this geometry with these operand prologues (single source of truth for
-// the bindings' checks and the Python autotuner's candidate lists)
-bool igemm_variant_is_patch(int v);
-bool igemm_variant_ok(int v, const ConvGeom& g, bool pro, bool bn_bwd_pro);
-bool igemm_dual_ok(int v, const ConvGeom& g);
+// What a tile variant is (kernel family, tile, waves, LDS stages, launcher) is one row of the
+// descriptor tables in conv.hip; the predicates below read those rows.
+bool igemm_variant_glds(int v);   // not the register-staged kernel: LDS-DMA or patch
 bool igemm_variant_patch(int v);  // the LDS-resident-patch 3x3 kernel
-bool igemm_patch_ok(const ConvGeom& g);  // block-output prologue (see igemm_glds)
+bool igemm_glds_ok(const ConvGeom& g, bool pro, bool bn_bwd_pro);  // LDS-DMA geometry rule
+bool igemm_patch_ok(const ConvGeom& g);                            // patch-kernel geometry rule
+// Can tile variant v run this geometry with these operand prologues and this epilogue mode: the
+// bindings' check, the launcher's check and the Python autotuner's candidate lists.  It is built
+// on the set of (prologue, epilogue) pairs the launcher instantiates for the variant's family;
+// of the epilogue it knows the one hole that depends on the tile (BN-backward prologue + mode 4
+// on an LDS-DMA tile above 256 x 128), the others are fusion checks of the igemm binding.
+bool igemm_variant_ok(int v, const ConvGeom& g, bool pro, bool bn_bwd_pro, int epi_mode = 0);
+bool igemm_dual_ok(int v, const ConvGeom& g);  // ... with the block-output prologue
 int igemm_block_m(int N);
 void conv_igemm_nt(const ConvGeom& g, const uint16_t* A, size_t a_elems, const uint16_t* B,
                    uint16_t* out, const float* bias, float* stats, const ConvFusion& f,

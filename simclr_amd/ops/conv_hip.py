@@ -4,7 +4,10 @@ Tensors: activations are logical NCHW / physical NHWC (``channels_last``) bf16; 
 consumed as OHWI bf16 (the flat store's shadow) and their gradients are produced as OHWI fp32
 directly into the flat gradient buffer.
 
-Pass decomposition (all on ``igemm_nt`` / ``wgrad_tn``):
+Pass decomposition (every pass is an implicit GEMM or a weight-gradient launch; which kernel
+family and tile runs it — register-staged ``igemm_nt`` / ``wgrad_tn``, LDS-DMA ``igemm_glds`` /
+``wgrad_glds`` / ``wgrad_pipe`` / ``wgrad_xp``, or the patch kernels — is the autotuned variant,
+one row of the descriptor tables in ``csrc/conv.hip``):
 
 * forward   : gather x with (stride s, pad p); epilogue also emits per-channel Σy, Σy² block
               partials that the following BatchNorm consumes instead of re-reading y.
@@ -53,11 +56,8 @@ def igemm_choose(ops, A, B, out, geom, bias=None, want_stats=False, pro=None, ep
         if dual is not None:
             if not ops.igemm_dual_ok(v, geom):
                 continue
-        elif not ops.igemm_variant_ok(v, geom, psc is not None, bnb is not None):
+        elif not ops.igemm_variant_ok(v, geom, psc is not None, bnb is not None, emode):
             continue  # e.g. LDS-DMA variants: C % 64 == 0, BN-apply prologue only on 1x1
-        if (bnb is not None and emode & 255 == 4 and ops.igemm_variant_glds(v)
-                and bm * ops.igemm_variant_bn(v) > 256 * 128):
-            continue  # BN-backward prologue + mode-4 epilogue: not instantiated at 256 x 256
         if want_stats and M % bm:
             continue
         if psc is not None and pseg % bm:

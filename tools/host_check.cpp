@@ -4,8 +4,14 @@
 // admissibility / split planning of conv.hip, the BatchNorm reduction planning of bn.hip and
 // the split / workspace arithmetic of ntxent.hip and eval.hip — over every convolution of
 // ResNet-18/50 at the CIFAR (32x32) and ImageNet (224x224) shapes, in all three passes.
+//
+// --dump prints the conv tile-variant tables and the admissibility / split planning of a fixed
+// geometry list as JSON rows, using only the API that tests/golden/conv_variant_table_v1.json was
+// recorded with (this file built with -DHOST_CHECK_V1_API against the tree before the variant
+// descriptor tables); tests/test_host_sanitizers.py compares the two row for row.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 
 #include "../simclr_amd/csrc/kernels.h"
@@ -90,9 +96,195 @@ void check_net(const char* name, bool bottleneck, int H0, bool imagenet, int bat
   }
 }
 
+// The geometries of the dump: every pinned shape of bench/tiles_mi355x.json, the parametrisations
+// of tests/test_gpu_kernels.py, and a few that the LDS-DMA / patch kernels must reject.
+const ConvGeom DUMP_GEOMS[] = {
+    // pinned tile
+    {1024, 1, 1, 128, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 2048, 1, 1, 1, 1, 0, 0, 2048},
+    {1024, 1, 1, 2048, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 128, 1, 1, 1, 1, 0, 0, 128},
+    {1024, 1, 1, 2048, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 2048, 1, 1, 1, 1, 0, 0, 2048},
+    {1024, 16, 16, 128, 16, 16, 1, 1, 1, 1, -1, -1, 0, 0, 128, 32, 32, 2, 2, 0, 0, 128},
+    {1024, 16, 16, 128, 16, 16, 1, 1, 1, 1, 1, 1, 0, 0, 512, 16, 16, 1, 1, 0, 0, 512},
+    {1024, 16, 16, 128, 16, 16, 1, 2, 1, 1, -1, -1, 0, 1, 128, 32, 32, 2, 2, 0, 1, 128},
+    {1024, 16, 16, 128, 16, 16, 2, 1, 1, 1, -1, -1, 1, 0, 128, 32, 32, 2, 2, 1, 0, 128},
+    {1024, 16, 16, 128, 16, 16, 2, 2, 1, 1, -1, -1, 1, 1, 128, 32, 32, 2, 2, 1, 1, 128},
+    {1024, 16, 16, 128, 16, 16, 3, 3, 1, 1, 1, 1, -1, -1, 128, 16, 16, 1, 1, 0, 0, 128},
+    {1024, 16, 16, 256, 16, 16, 1, 1, 1, 1, 1, 1, 0, 0, 512, 16, 16, 1, 1, 0, 0, 512},
+    {1024, 16, 16, 256, 8, 8, 3, 3, 2, 2, 1, 1, -1, -1, 256, 8, 8, 1, 1, 0, 0, 256},
+    {1024, 16, 16, 512, 16, 16, 1, 1, 1, 1, 1, 1, 0, 0, 128, 16, 16, 1, 1, 0, 0, 128},
+    {1024, 16, 16, 512, 16, 16, 1, 1, 1, 1, 1, 1, 0, 0, 256, 16, 16, 1, 1, 0, 0, 256},
+    {1024, 16, 16, 512, 8, 8, 1, 1, 2, 2, 1, 1, 0, 0, 1024, 8, 8, 1, 1, 0, 0, 1024},
+    {1024, 32, 32, 128, 16, 16, 3, 3, 2, 2, 1, 1, -1, -1, 128, 16, 16, 1, 1, 0, 0, 128},
+    {1024, 32, 32, 128, 32, 32, 1, 1, 1, 1, 1, 1, 0, 0, 256, 32, 32, 1, 1, 0, 0, 256},
+    {1024, 32, 32, 256, 16, 16, 1, 1, 2, 2, 1, 1, 0, 0, 512, 16, 16, 1, 1, 0, 0, 512},
+    {1024, 32, 32, 256, 32, 32, 1, 1, 1, 1, 1, 1, 0, 0, 128, 32, 32, 1, 1, 0, 0, 128},
+    {1024, 32, 32, 256, 32, 32, 1, 1, 1, 1, 1, 1, 0, 0, 64, 32, 32, 1, 1, 0, 0, 64},
+    {1024, 32, 32, 64, 32, 32, 1, 1, 1, 1, 1, 1, 0, 0, 256, 32, 32, 1, 1, 0, 0, 256},
+    {1024, 32, 32, 64, 32, 32, 1, 1, 1, 1, 1, 1, 0, 0, 64, 32, 32, 1, 1, 0, 0, 64},
+    {1024, 32, 32, 64, 32, 32, 3, 3, 1, 1, 1, 1, -1, -1, 64, 32, 32, 1, 1, 0, 0, 64},
+    {1024, 32, 32, 8, 32, 32, 3, 3, 1, 1, 1, 1, -1, -1, 64, 32, 32, 1, 1, 0, 0, 64},
+    {1024, 4, 4, 2048, 4, 4, 1, 1, 1, 1, 1, 1, 0, 0, 1024, 4, 4, 1, 1, 0, 0, 1024},
+    {1024, 4, 4, 2048, 4, 4, 1, 1, 1, 1, 1, 1, 0, 0, 512, 4, 4, 1, 1, 0, 0, 512},
+    {1024, 4, 4, 512, 4, 4, 1, 1, 1, 1, -1, -1, 0, 0, 512, 8, 8, 2, 2, 0, 0, 512},
+    {1024, 4, 4, 512, 4, 4, 1, 1, 1, 1, 1, 1, 0, 0, 2048, 4, 4, 1, 1, 0, 0, 2048},
+    {1024, 4, 4, 512, 4, 4, 1, 2, 1, 1, -1, -1, 0, 1, 512, 8, 8, 2, 2, 0, 1, 512},
+    {1024, 4, 4, 512, 4, 4, 2, 1, 1, 1, -1, -1, 1, 0, 512, 8, 8, 2, 2, 1, 0, 512},
+    {1024, 4, 4, 512, 4, 4, 2, 2, 1, 1, -1, -1, 1, 1, 512, 8, 8, 2, 2, 1, 1, 512},
+    {1024, 4, 4, 512, 4, 4, 3, 3, 1, 1, 1, 1, -1, -1, 512, 4, 4, 1, 1, 0, 0, 512},
+    {1024, 8, 8, 1024, 4, 4, 1, 1, 2, 2, 1, 1, 0, 0, 2048, 4, 4, 1, 1, 0, 0, 2048},
+    {1024, 8, 8, 1024, 8, 8, 1, 1, 1, 1, 1, 1, 0, 0, 256, 8, 8, 1, 1, 0, 0, 256},
+    {1024, 8, 8, 1024, 8, 8, 1, 1, 1, 1, 1, 1, 0, 0, 512, 8, 8, 1, 1, 0, 0, 512},
+    {1024, 8, 8, 256, 8, 8, 1, 1, 1, 1, -1, -1, 0, 0, 256, 16, 16, 2, 2, 0, 0, 256},
+    {1024, 8, 8, 256, 8, 8, 1, 1, 1, 1, 1, 1, 0, 0, 1024, 8, 8, 1, 1, 0, 0, 1024},
+    {1024, 8, 8, 256, 8, 8, 1, 2, 1, 1, -1, -1, 0, 1, 256, 16, 16, 2, 2, 0, 1, 256},
+    {1024, 8, 8, 256, 8, 8, 2, 1, 1, 1, -1, -1, 1, 0, 256, 16, 16, 2, 2, 1, 0, 256},
+    {1024, 8, 8, 256, 8, 8, 2, 2, 1, 1, -1, -1, 1, 1, 256, 16, 16, 2, 2, 1, 1, 256},
+    {1024, 8, 8, 256, 8, 8, 3, 3, 1, 1, 1, 1, -1, -1, 256, 8, 8, 1, 1, 0, 0, 256},
+    {1024, 8, 8, 512, 4, 4, 3, 3, 2, 2, 1, 1, -1, -1, 512, 4, 4, 1, 1, 0, 0, 512},
+    {1024, 8, 8, 512, 8, 8, 1, 1, 1, 1, 1, 1, 0, 0, 1024, 8, 8, 1, 1, 0, 0, 1024},
+    // test_conv_fwd_dgrad_wgrad
+    {4, 8, 8, 64, 8, 8, 3, 3, 1, 1, 1, 1, -1, -1, 64, 8, 8, 1, 1, 0, 0, 64},
+    {3, 9, 9, 64, 5, 5, 3, 3, 2, 2, 1, 1, -1, -1, 128, 5, 5, 1, 1, 0, 0, 128},
+    {2, 8, 8, 128, 8, 8, 1, 1, 1, 1, 1, 1, 0, 0, 256, 8, 8, 1, 1, 0, 0, 256},
+    {2, 8, 8, 256, 4, 4, 1, 1, 2, 2, 1, 1, 0, 0, 512, 4, 4, 1, 1, 0, 0, 512},
+    {5, 8, 8, 8, 12, 12, 3, 3, 1, 1, 1, 1, -3, -3, 64, 12, 12, 1, 1, 0, 0, 64},
+    {2, 16, 16, 8, 8, 8, 7, 7, 2, 2, 1, 1, -3, -3, 64, 8, 8, 1, 1, 0, 0, 64},
+    {1, 5, 5, 64, 5, 5, 3, 3, 1, 1, 1, 1, -1, -1, 64, 5, 5, 1, 1, 0, 0, 64},
+    // test_igemm_variants_prologue_epilogue
+    {8, 16, 16, 64, 16, 16, 1, 1, 1, 1, 1, 1, 0, 0, 128, 16, 16, 1, 1, 0, 0, 128},
+    {8, 16, 16, 64, 16, 16, 3, 3, 1, 1, 1, 1, -1, -1, 128, 16, 16, 1, 1, 0, 0, 128},
+    {8, 16, 16, 64, 8, 8, 3, 3, 2, 2, 1, 1, -1, -1, 128, 8, 8, 1, 1, 0, 0, 128},
+    // test_igemm_block_output_prologue
+    {16, 16, 16, 256, 16, 16, 1, 1, 1, 1, 1, 1, 0, 0, 64, 16, 16, 1, 1, 0, 0, 64},
+    {16, 8, 8, 512, 8, 8, 1, 1, 1, 1, 1, 1, 0, 0, 128, 8, 8, 1, 1, 0, 0, 128},
+    {16, 4, 4, 1024, 4, 4, 1, 1, 1, 1, 1, 1, 0, 0, 256, 4, 4, 1, 1, 0, 0, 256},
+    {16, 4, 4, 2048, 4, 4, 1, 1, 1, 1, 1, 1, 0, 0, 512, 4, 4, 1, 1, 0, 0, 512},
+    // test_igemm_glds_variants
+    {8, 16, 16, 64, 16, 16, 1, 1, 1, 1, 1, 1, 0, 0, 256, 16, 16, 1, 1, 0, 0, 256},
+    {8, 16, 16, 64, 16, 16, 3, 3, 1, 1, 1, 1, -1, -1, 64, 16, 16, 1, 1, 0, 0, 64},
+    {8, 16, 16, 128, 8, 8, 3, 3, 2, 2, 1, 1, -1, -1, 192, 8, 8, 1, 1, 0, 0, 192},
+    {8, 16, 16, 128, 8, 8, 1, 1, 2, 2, 1, 1, 0, 0, 128, 8, 8, 1, 1, 0, 0, 128},
+    {8, 16, 16, 128, 16, 16, 3, 3, 1, 1, 1, 1, -1, -1, 512, 16, 16, 1, 1, 0, 0, 512},
+    {8, 32, 32, 64, 32, 32, 3, 3, 1, 1, 1, 1, -1, -1, 64, 32, 32, 1, 1, 0, 0, 64},
+    {8, 32, 32, 128, 32, 32, 3, 3, 1, 1, 1, 1, -1, -1, 128, 32, 32, 1, 1, 0, 0, 128},
+    // test_wgrad_glds_variants
+    {8, 4, 4, 256, 4, 4, 3, 3, 1, 1, 1, 1, -1, -1, 512, 4, 4, 1, 1, 0, 0, 512},
+    {8, 5, 5, 64, 5, 5, 3, 3, 1, 1, 1, 1, -1, -1, 64, 5, 5, 1, 1, 0, 0, 64},
+    {8, 16, 16, 128, 16, 16, 3, 3, 1, 1, 1, 1, -1, -1, 128, 16, 16, 1, 1, 0, 0, 128},
+    {8, 32, 32, 128, 32, 32, 3, 3, 1, 1, 1, 1, -1, -1, 64, 32, 32, 1, 1, 0, 0, 64},
+    {8, 8, 8, 64, 8, 8, 3, 3, 1, 1, 1, 1, -1, -1, 128, 8, 8, 1, 1, 0, 0, 128},
+    {8, 8, 8, 64, 4, 4, 3, 3, 2, 2, 1, 1, -1, -1, 64, 4, 4, 1, 1, 0, 0, 64},
+    // stride-2 dgrad parity class (0, 0)
+    {8, 8, 8, 128, 8, 8, 1, 1, 1, 1, -1, -1, 0, 0, 128, 16, 16, 2, 2, 0, 0, 128},
+    // stride-2 dgrad parity class (0, 1)
+    {8, 8, 8, 128, 8, 8, 1, 2, 1, 1, -1, -1, 0, 1, 128, 16, 16, 2, 2, 0, 1, 128},
+    // stride-2 dgrad parity class (1, 0)
+    {8, 8, 8, 128, 8, 8, 2, 1, 1, 1, -1, -1, 1, 0, 128, 16, 16, 2, 2, 1, 0, 128},
+    // stride-2 dgrad parity class (1, 1)
+    {8, 8, 8, 128, 8, 8, 2, 2, 1, 1, -1, -1, 1, 1, 128, 16, 16, 2, 2, 1, 1, 128},
+    // stride-2 dgrad parity class (0, 0)
+    {8, 16, 16, 128, 16, 16, 1, 1, 1, 1, -1, -1, 0, 0, 64, 32, 32, 2, 2, 0, 0, 64},
+    // stride-2 dgrad parity class (0, 1)
+    {8, 16, 16, 128, 16, 16, 1, 2, 1, 1, -1, -1, 0, 1, 64, 32, 32, 2, 2, 0, 1, 64},
+    // stride-2 dgrad parity class (1, 0)
+    {8, 16, 16, 128, 16, 16, 2, 1, 1, 1, -1, -1, 1, 0, 64, 32, 32, 2, 2, 1, 0, 64},
+    // stride-2 dgrad parity class (1, 1)
+    {8, 16, 16, 128, 16, 16, 2, 2, 1, 1, -1, -1, 1, 1, 64, 32, 32, 2, 2, 1, 1, 64},
+    // stride-2 dgrad parity class (0, 0)
+    {8, 8, 8, 256, 8, 8, 1, 1, 1, 1, -1, -1, 0, 0, 128, 16, 16, 2, 2, 0, 0, 128},
+    {8, 4, 4, 256, 4, 4, 1, 1, 1, 1, -1, -1, 0, 0, 256, 8, 8, 2, 2, 0, 0, 256},
+    // stride-2 dgrad parity class (0, 1)
+    {8, 4, 4, 256, 4, 4, 1, 2, 1, 1, -1, -1, 0, 1, 256, 8, 8, 2, 2, 0, 1, 256},
+    // stride-2 dgrad parity class (1, 0)
+    {8, 4, 4, 256, 4, 4, 2, 1, 1, 1, -1, -1, 1, 0, 256, 8, 8, 2, 2, 1, 0, 256},
+    // stride-2 dgrad parity class (1, 1)
+    {8, 4, 4, 256, 4, 4, 2, 2, 1, 1, -1, -1, 1, 1, 256, 8, 8, 2, 2, 1, 1, 256},
+    // test_wgrad_bn_backward_prologue_padded_channels (C = 8 stem)
+    {16, 32, 32, 8, 32, 32, 3, 3, 1, 1, 1, 1, -1, -1, 64, 32, 32, 1, 1, 0, 0, 64},
+    {16, 32, 32, 8, 36, 36, 3, 3, 1, 1, 1, 1, -3, -3, 64, 36, 36, 1, 1, 0, 0, 64},
+    // rejected by LDS-DMA: C % 64 != 0
+    {8, 16, 16, 96, 16, 16, 1, 1, 1, 1, 1, 1, 0, 0, 128, 16, 16, 1, 1, 0, 0, 128},
+    {8, 16, 16, 32, 16, 16, 3, 3, 1, 1, 1, 1, -1, -1, 64, 16, 16, 1, 1, 0, 0, 64},
+    // padded 3x3 off the patch geometry (C = 256): no prologue on LDS-DMA
+    {8, 16, 16, 256, 16, 16, 3, 3, 1, 1, 1, 1, -1, -1, 256, 16, 16, 1, 1, 0, 0, 256},
+    // patch kernel rejects OW = 8
+    {8, 8, 8, 64, 8, 8, 3, 3, 1, 1, 1, 1, -1, -1, 64, 8, 8, 1, 1, 0, 0, 64},
+    // patch kernel rejects OW = 64
+    {4, 64, 64, 64, 64, 64, 3, 3, 1, 1, 1, 1, -1, -1, 64, 64, 64, 1, 1, 0, 0, 64},
+};
+
+template <class F>
+unsigned mask_of(int n, F ok) {
+  unsigned m = 0;
+  for (int v = 0; v < n; ++v) m |= ok(v) ? 1u << v : 0u;
+  return m;
+}
+
+void dump() {
+  const int ni = igemm_num_variants(), nw = wgrad_num_variants();
+  std::printf("[\n{\"igemm_variants\": %d, \"wgrad_variants\": %d}", ni, nw);
+  for (int v = 0; v < ni; ++v)
+    std::printf(",\n{\"igemm\": %d, \"bm\": %d, \"bn\": %d, \"glds\": %d, \"patch\": %d}", v,
+                igemm_variant_bm(v), igemm_variant_bn(v), (int)igemm_variant_glds(v),
+                (int)igemm_variant_patch(v));
+  for (int v = 0; v < nw; ++v)
+    std::printf(",\n{\"wgrad\": %d, \"glds\": %d, \"area\": %d}", v, (int)wgrad_variant_glds(v),
+                wgrad_variant_area(v));
+  for (const ConvGeom& g : DUMP_GEOMS) {
+    std::printf(",\n{\"geom\": [");
+    const int* p = &g.Nb;
+    for (int i = 0; i < 22; ++i) std::printf("%s%d", i ? ", " : "", p[i]);
+    std::printf("], \"igemm_ok\": [");  // (pro, bn_bwd_pro) = (0,0) (1,0) (0,1) (1,1)
+    for (int c = 0; c < 4; ++c)
+      std::printf("%s%u", c ? ", " : "",
+                  mask_of(ni, [&](int v) { return igemm_variant_ok(v, g, c & 1, c >> 1); }));
+    std::printf("], \"dual_ok\": %u, \"wgrad_ok\": [",
+                mask_of(ni, [&](int v) { return igemm_dual_ok(v, g); }));
+    for (int c = 0; c < 4; ++c)  // (pro, dy_pro) in the same order
+      std::printf("%s%u", c ? ", " : "",
+                  mask_of(nw, [&](int v) { return wgrad_variant_ok(v, g, c & 1, c >> 1); }));
+    std::printf("], \"splits_tiles\": [");  // [variant, splits, tiles] of every admissible one
+    const char* sep = "";
+    for (int v = 0; v < nw; ++v)
+      if (wgrad_variant_ok(v, g, false, false)) {
+        std::printf("%s[%d, %d, %d]", sep, v, wgrad_splits(g, v), wgrad_tiles(g, v));
+        sep = ", ";
+      }
+    std::printf("]}");
+  }
+  std::printf("\n]\n");
+}
+
+#ifndef HOST_CHECK_V1_API
+// the epilogue argument of igemm_variant_ok: modes 0-3 change nothing, and the BN-backward
+// prologue with the mode-4 epilogue leaves the LDS-DMA tiles of at most 256 x 128
+void check_epilogue_rule() {
+  for (const ConvGeom& g : DUMP_GEOMS)
+    for (int v = 0; v < igemm_num_variants(); ++v) {
+      const bool big = igemm_variant_glds(v) &&
+                       igemm_variant_bm(v) * igemm_variant_bn(v) > 256 * 128;
+      for (int c = 0; c < 4; ++c) {
+        const bool pro = c & 1, bnb = c >> 1, base = igemm_variant_ok(v, g, pro, bnb);
+        for (int e = 0; e < 4; ++e)
+          EXPECT(igemm_variant_ok(v, g, pro, bnb, e) == base, "variant %d epilogue %d", v, e);
+        if (bnb)
+          EXPECT(igemm_variant_ok(v, g, pro, true, 4) == (base && !big), "variant %d mode 4", v);
+      }
+    }
+}
+#endif
+
 }  // namespace
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "--dump")) {
+    unsetenv("SIMCLR_WGRAD_TARGET_PCT");  // the recorded split counts are the default target's
+    dump();
+    return 0;
+  }
+#ifndef HOST_CHECK_V1_API
+  check_epilogue_rule();
+#endif
   for (int batch : {64, 1024}) {
     check_net("resnet50-cifar", true, 32, false, batch);
     check_net("resnet18-cifar", false, 36, false, batch);
