@@ -36,13 +36,15 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass, field
-from typing import List, Optional, Tuple
+from typing import List, NamedTuple, Optional, Tuple, Union
 
 import torch
 import torch.distributed as dist
 
 from ..ops import _ext
-from ..ops.conv_hip import (fwd_geom, igemm_choose, igemm_launch, run_wgrad, shadow_ohwi)
+from ..ops.conv_hip import (BlockOut, BnApply, BnBackward, Epilogue, Igemm, StatsOut, WgradDY,
+                            WgradX, DgradLaunch, dgrad_plan, fwd_geom, run_wgrad, shadow_ohwi,
+                            wt_shape)
 from ..parallel import state as pstate
 from ..parallel.state import site_key
 
@@ -128,11 +130,68 @@ class _BlockTape:
     pool: Optional[Tuple[torch.Tensor, torch.Tensor]] = None
 
 
+class LazyBN(NamedTuple):
+    """A BatchNorm backward left to its consumers' operand prologues: dy = coef.A·g +
+    coef.B·a + coef.D is computed on the fly and never written to HBM."""
+    a: torch.Tensor                     # the BN's input (pre-BN conv output)
+    coef: torch.Tensor                  # [3][S][C] (_bn_bwd_finish)
+
+
+class BlockOutput(NamedTuple):
+    """A block output not formed yet: out = relu(bn(aL) + res'), mask = its ReLU bitmask."""
+    aL: torch.Tensor                    # the block's last pre-BN activation
+    ss: torch.Tensor                    # its BN scale / shift [2][S][C]
+    res: torch.Tensor                   # residual: block input, or the downsample's pre-BN output
+    rss: Optional[torch.Tensor]         # the downsample BN's scale / shift (None: identity)
+    out: torch.Tensor
+    mask: torch.Tensor
+
+
+# The records below keep a leading ``kind`` tag and the field order of the plain tuples they
+# name, so a caller may pass either and positional readers (tests' recorders) keep working.
+
+class MaskEpi(NamedTuple):
+    """dgrad epilogue of a BN + ReLU producer (mode 3): g = dx·[bn(a_prev) > 0]."""
+    kind: str                           # "mask"
+    a_prev: torch.Tensor
+    bs: _BNState
+
+
+class ResEpi(NamedTuple):
+    """dgrad epilogue of a residual-block producer (mode 4): g = (dx + resid)·[y > 0].
+    ``mask``: the ReLU bitmask of its output y, ``a_prev`` / ``mi`` its last pre-BN activation
+    and BN mean / invstd; ``resid`` may alias dx.  With ``ad`` / ``mid`` (its downsample's
+    pre-BN activation and mean / invstd) the partials of the downsample BN too."""
+    kind: str                           # "res"
+    resid: torch.Tensor
+    mask: torch.Tensor
+    a_prev: torch.Tensor
+    mi: torch.Tensor
+    ad: Optional[torch.Tensor] = None
+    mid: Optional[torch.Tensor] = None
+
+
+class BnBwdLocal(NamedTuple):
+    """A started BN backward that one fused launch finishes (single GPU / IPC exchange)."""
+    kind: str                           # "local"
+    bn: torch.nn.Module
+    partial: torch.Tensor
+    nblk_seg: int
+    bs: _BNState
+    ipc: object
+
+
+class BnBwdDist(NamedTuple):
+    """A started BN backward whose local sums are being all-reduced (``work``)."""
+    kind: str                           # "dist"
+    bn: torch.nn.Module
+    sums: torch.Tensor
+    work: object
+    bs: _BNState
+
+
 # persistent blocks per view segment of the fused 1x1 backward (2 segments: 2x this many blocks)
 _BWD1X1_BPS = 128
-
-# bit 8 of the igemm epilogue mode: the residual operand is stride-2 subsampled (conv.hip)
-_EPI_SUB = 256
 
 
 class FusedStages:
@@ -338,7 +397,7 @@ class FusedStages:
 
     # ------------------------------------------------------------------ building blocks
     def _conv_bn_fwd(self, ops, xn, cs: _ConvSpec, pro_ss: Optional[torch.Tensor], S: int, st,
-                     dual=None, slot: int = 0):
+                     dual: Optional[BlockOutput] = None, slot: int = 0):
         """a = conv(pro(x)) and the BatchNorm state of ``cs.bn`` over it (statistics partials
         from the conv epilogue, one reduce / finalize launch)."""
         a, partial, nblk = self._conv_fwd(ops, xn, cs, pro_ss, S, dual=dual)
@@ -384,12 +443,12 @@ class FusedStages:
         out.view(Co, 7, 7, Ci).copy_(g8[:, :7, :7, :Ci])
 
     def _conv_fwd(self, ops, xn, cs: _ConvSpec, pro_ss: Optional[torch.Tensor], S: int,
-                  dual=None):
+                  dual: Optional[BlockOutput] = None):
         """a = conv(pro(x)) with BN statistics partials in the epilogue.
 
-        ``dual = (aL, ss, res, rss, out, mask)``: the input is the previous block's output,
-        formed in this conv's prologue from that block's conv3 activation ``aL`` and residual
-        ``res`` and written to ``out`` / ``mask`` by the same kernel (``xn`` is ``out``).
+        ``dual``: the input is the previous block's output, formed in this conv's prologue from
+        that block's last activation ``aL`` and residual ``res`` and written to ``out`` /
+        ``mask`` by the same kernel (``xn`` is ``out``).
         Returns (a, partials, blocks per segment); the caller reduces the partials
         (``_bn_fwd``)."""
         Nb, H, W, C = xn.shape
@@ -405,17 +464,18 @@ class FusedStages:
             w = shadow_ohwi(cs.conv.weight, C)
             g = fwd_geom(Nb, H, W, C, OH, OW, cs.k, cs.k, cs.stride, cs.pad, Co)
         M = Nb * OH * OW
-        pro, dl, A = None, None, xn
+        pro, A = None, xn
         if dual is not None:
-            aL, ss, res, rss, out, mask = dual
-            pro = (ss[0], ss[1], M // S, True)
-            dl, A = (res, None if rss is None else rss.view(-1), out, mask), aL
+            pro = BlockOut(dual.ss[0], dual.ss[1], M // S, dual.res,
+                           None if dual.rss is None else dual.rss.view(-1), dual.out, dual.mask)
+            A = dual.aL
         elif pro_ss is not None:
-            pro = (pro_ss[0], pro_ss[1], M // S, True)
-        v = igemm_choose(ops, A, w, a, g, want_stats=True, pro=pro, seg_rows=M // S, dual=dl)
+            pro = BnApply(pro_ss[0], pro_ss[1], M // S)
+        job = Igemm(A, w, a, g, want_stats=True, pro=pro, seg_rows=M // S)
+        v = job.choose(ops)
         bm = ops.igemm_variant_bm(v)
         stats = torch.empty(((M // bm) * 2 * Co,), device=xn.device, dtype=torch.float32)
-        igemm_launch(ops, A, w, a, g, v, stats=stats, pro=pro, dual=dl)
+        job.launch(ops, v, StatsOut(stats))
         return a, stats, M // bm // S
 
     def _dual_ok(self, ops, xn, cs: _ConvSpec, S: int) -> bool:
@@ -451,17 +511,18 @@ class FusedStages:
         if not st.comm or ipc is not None:
             # one launch: reduce + finalize (last-arriver); at world > 1 the IPC statistics
             # exchange runs inside it (comm/ipc.py)
-            ops.bn_reduce_fused(partial, nblk_seg, S, C, 1, None, count, bn.eps, bn.momentum,
-                                bn.running_mean, bn.running_var, mi, bn.num_batches_tracked,
-                                bn.weight.detach(), bn.bias.detach(), ss, None, None, None, slot,
+            ops.bn_reduce_fused(partial, nblk_seg, S, C, 1, count=count, eps=bn.eps,
+                                momentum=bn.momentum, rm=bn.running_mean, rv=bn.running_var,
+                                mi=mi, nbt=bn.num_batches_tracked, gamma=bn.weight.detach(),
+                                beta=bn.bias.detach(), ss=ss, ticket_slot=slot,
                                 **(ipc.kwargs(site_key(bn, "fwd"), S, C) if ipc is not None else {}))
         else:
             stats = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
-            ops.bn_reduce_fused(partial, nblk_seg, S, C, 0, stats, ticket_slot=slot)
+            ops.bn_reduce_fused(partial, nblk_seg, S, C, 0, stats=stats, ticket_slot=slot)
             _allreduce(stats, st, branch=slot == 1)
             ops.bn_finalize(stats, S, C, count, bn.eps, bn.momentum, bn.running_mean,
-                            bn.running_var, mi, bn.num_batches_tracked, bn.weight.detach(),
-                            bn.bias.detach(), ss)
+                            bn.running_var, mi, bn.num_batches_tracked,
+                            gamma=bn.weight.detach(), beta=bn.bias.detach(), ss=ss)
         return _BNState(mi, ss.view(2, S * C), count)
 
     def _deliver_bn_grads(self, bn, run) -> None:
@@ -491,35 +552,33 @@ class FusedStages:
         to wait for (one fused launch in the finish)."""
         C = bn.num_features
         if not st.comm or st.ipc is not None:
-            return ("local", bn, partial, nblk_seg, bs, st.ipc)
+            return BnBwdLocal("local", bn, partial, nblk_seg, bs, st.ipc)
         dev = partial.device
         sums = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
         # one launch: the local sums (all-reduced below) and dγ, dβ from them
         self._deliver_bn_grads(bn, lambda dg, db: ops.bn_reduce_fused(
-            partial, nblk_seg, S, C, 0, sums, dgamma=dg, dbeta=db))
+            partial, nblk_seg, S, C, 0, stats=sums, dgamma=dg, dbeta=db))
         work = dist.all_reduce(sums, group=st.stats_group, async_op=True)
-        return ("dist", bn, sums, work, bs)
+        return BnBwdDist("dist", bn, sums, work, bs)
 
-    def _bn_bwd_finish(self, ops, h, S: int) -> torch.Tensor:
+    def _bn_bwd_finish(self, ops, h: Union[BnBwdLocal, BnBwdDist], S: int) -> torch.Tensor:
         """Phase 2: coef [3][S][C] for the input gradient (from the global sums)."""
-        bn, bs = h[1], h[4]
+        bn, bs = h.bn, h.bs
         C = bn.num_features
         dev = bs.mi.device
         coef = torch.empty((3 * S * C,), device=dev, dtype=torch.float32)
         if _SKIP_BNRED in ("bwd", "all"):
             return coef
-        if h[0] == "local":
+        if isinstance(h, BnBwdLocal):
             # single launch; with the IPC exchange dγ, dβ come from the local sums and coef
             # from the global ones (SyncBN semantics, see _bn_bwd_start)
-            partial, nblk_seg, ipc = h[2], h[3], h[5]
-            kw = ipc.kwargs(site_key(bn, "bwd"), S, C) if ipc is not None else {}
+            kw = h.ipc.kwargs(site_key(bn, "bwd"), S, C) if h.ipc is not None else {}
             self._deliver_bn_grads(bn, lambda dg, db: ops.bn_reduce_fused(
-                partial, nblk_seg, S, C, 2, None, bs.count, 0.0, 0.0, None, None, bs.mi,
-                None, bn.weight.detach(), None, None, dg, db, coef, **kw))
+                h.partial, h.nblk_seg, S, C, 2, count=bs.count, eps=0.0, momentum=0.0, mi=bs.mi,
+                gamma=bn.weight.detach(), dgamma=dg, dbeta=db, coef=coef, **kw))
         else:
-            sums, work = h[2], h[3]
-            work.wait()
-            ops.bn_bwd_finalize(sums, bs.mi, bn.weight.detach(), S, C, bs.count, None, None,
+            h.work.wait()
+            ops.bn_bwd_finalize(h.sums, bs.mi, bn.weight.detach(), S, C, bs.count, None, None,
                                 coef)
         return coef
 
@@ -528,9 +587,9 @@ class FusedStages:
                                    S)
 
     def _wgrad(self, ops, dyn, xn, cs: _ConvSpec, pro_ss: Optional[torch.Tensor], S: int,
-               bnb: Optional[Tuple] = None, main: bool = False):
-        """``bnb = (a, coef)``: dy = coef.A·dyn + coef.B·a + coef.D, the BatchNorm backward of
-        the conv's own BN, computed in the dY operand's prologue (never written to HBM)."""
+               bnb: Optional[LazyBN] = None, main: bool = False):
+        """``bnb``: dy = coef.A·dyn + coef.B·a + coef.D, the BatchNorm backward of the conv's
+        own BN, computed in the dY operand's prologue (never written to HBM)."""
         Nb, H, W, C = xn.shape
         Co = cs.conv.out_channels
         OH, OW = dyn.shape[1], dyn.shape[2]
@@ -543,8 +602,8 @@ class FusedStages:
         M = Nb * OH * OW
         pro = None
         if pro_ss is not None:
-            pro = (pro_ss[0], pro_ss[1], M // S, True, S)
-        dpro = (bnb[0], bnb[1], M // S, S) if bnb is not None else None
+            pro = WgradX(pro_ss[0], pro_ss[1], M // S, True, S)
+        dpro = WgradDY(*bnb, M // S, S) if bnb is not None else None
 
         side = getattr(self, "_side", None) if getattr(self, "wgrad_stream", False) else None
         concurrent = side is not None and not main
@@ -603,7 +662,7 @@ class FusedStages:
                       xin: Optional[torch.Tensor] = None):
         """conv3 dgrad (mode-3 epilogue of BN2) + weight gradient in one launch; the weight
         gradient's split reduction runs on the side stream.  Returns (gm, partials, blocks per
-        segment) like ``_dgrad`` with ``bn_epi=("mask", ...)``.  ``xin``: the conv's forward
+        segment) like ``_dgrad`` with a ``MaskEpi``.  ``xin``: the conv's forward
         input when it was materialised (relu(bn2(a2)); wide form only)."""
         Nb, H, W, Ci = a_prev.shape
         Co = cs.conv.out_channels
@@ -614,12 +673,13 @@ class FusedStages:
         bps = self._bwd1x1_bps(M // S, self.bwd1x1_bps_wide if wide else self.bwd1x1_bps)
         xraw = xin if (wide and xin is not None and xin is not a_prev) else None
         w = shadow_ohwi(cs.conv.weight, Ci)
-        wt = self._dgrad_weight(ops, cs, w, (0, 0), [Co, 1, 1, Ci, 1, 1, 0, -1, 0, -1])
+        wt = self._dgrad_weight(ops, cs, w,
+                                dgrad_plan(Nb, H, W, Ci, H, W, Co, 1, 1, 0).launches[0])
         dev = dyn.device
         gm = _empty_nhwc(Nb, H, W, Ci, dev)
         stats = torch.empty((S * bps * 2 * Ci,), device=dev, dtype=torch.float32)
         wpart = torch.empty((S * bps * Co * Ci,), device=dev, dtype=torch.float32)
-        a3, coef = (bnb[0], bnb[1]) if bnb is not None else (None, None)
+        a3, coef = bnb if bnb is not None else (None, None)
         if xraw is not None:  # X = the materialised relu(bn2(a2)); a2 for the epilogue
             ops.conv1x1_bwd_dual(dyn, a3, coef, xraw, bs_prev.ss.view(-1), bs_prev.mi.view(-1),
                                  wt, gm, stats, wpart, S, bps, a_prev)
@@ -686,7 +746,8 @@ class FusedStages:
             ops.bn_bwd_apply(g3, None, tp.ad, coefd, S, False, dad, None)
             bps = self._bwd1x1_bps(Nb * OH * OW // S, 32)
             w = shadow_ohwi(cs.conv.weight, Ci)
-            wt = self._dgrad_weight(ops, cs, w, (0, 0), [Co, 1, 1, Ci, 1, 1, 0, 2, 0, 2])
+            wt = self._dgrad_weight(ops, cs, w, dgrad_plan(Nb, H, W, Ci, OH, OW, Co, 1, 2, 0,
+                                                           compact=True).launches[0])
             resid = _empty_nhwc(Nb, OH, OW, Ci, dev)
             wpart = torch.empty((S * bps * Co * Ci,), device=dev, dtype=torch.float32)
             ops.conv1x1_bwd_dual_s2(dad, None, None, tp.x, wt, resid, wpart, S, bps)
@@ -694,7 +755,8 @@ class FusedStages:
             M = Nb * H * W
             bps = self._bwd1x1_bps(M // S, self.bwd1x1_bps)
             w = shadow_ohwi(cs.conv.weight, Ci)
-            wt = self._dgrad_weight(ops, cs, w, (0, 0), [Co, 1, 1, Ci, 1, 1, 0, -1, 0, -1])
+            wt = self._dgrad_weight(ops, cs, w,
+                                    dgrad_plan(Nb, H, W, Ci, H, W, Co, 1, 1, 0).launches[0])
             resid = _empty_nhwc(Nb, H, W, Ci, dev)
             wpart = torch.empty((S * bps * Co * Ci,), device=dev, dtype=torch.float32)
             nostats = torch.empty((1,), device=dev, dtype=torch.float32)
@@ -764,7 +826,7 @@ class FusedStages:
         key = (Nb, H, W, C, Ci)
         cache = self.__dict__.setdefault("_patch_bnb_cache", {})
         if key not in cache:
-            g = [Nb, H, W, C, H, W, 3, 3, 1, 1, 1, 1, -1, -1, Ci, H, W, 1, 1, 0, 0, Ci]
+            g = dgrad_plan(Nb, H, W, Ci, H, W, C, 3, 1, 1).launches[0].geom
             cache[key] = any(ops.igemm_variant_patch(v) and ops.igemm_variant_ok(v, g, True, True)
                              for v in range(ops.igemm_nvariants()))
         return cache[key]
@@ -778,23 +840,19 @@ class FusedStages:
                 and M % S == 0 and (M // S) % 256 == 0)
 
     def _dgrad(self, ops, dyn, cs: _ConvSpec, in_shape, S: int, accumulate: bool = False,
-               dx: Optional[torch.Tensor] = None, bn_epi: Optional[Tuple] = None,
-               bnb: Optional[Tuple] = None, compact: bool = False,
-               sub_resid: bool = False, bnb_out: Optional[torch.Tensor] = None):
+               dx: Optional[torch.Tensor] = None,
+               bn_epi: Union[None, MaskEpi, ResEpi] = None, bnb: Optional[LazyBN] = None,
+               compact: bool = False, sub_resid: bool = False,
+               bnb_out: Optional[torch.Tensor] = None):
         """dx (NHWC) = conv-transpose(dy).  ``accumulate``: dx += result (dx must be given).
 
-        ``bn_epi`` selects a BatchNorm-backward epilogue that also returns Σg, Σg·x̂ partials
-        (segment-major across stride-2 parity classes) → (dx, partial, blocks_per_segment):
-          ("mask", a_prev, bn_state)      mode 3: g = dx·[bn(a_prev) > 0] (BN+ReLU producer)
-          ("res", resid, mask, a_prev, mi, ad, mid)
-                                          mode 4: g = (dx + resid)·[y > 0] (residual-block
-                                          producer: mask = its output's ReLU bitmask, a_prev =
-                                          its last pre-BN activation; resid may alias dx); with
-                                          ``ad`` (the producer's downsample pre-BN activation)
-                                          the partials of its downsample BN too → (p3, pd)
-        ``bnb = (a, coef)`` (1x1 stride-1; 3x3 stride-1 on the patch kernel with ``bnb_out``):
-        the A operand is the BatchNorm backward coef.A·dyn + coef.B·a + coef.D computed in the
-        prologue; ``bnb_out`` receives that operand (the weight gradient's dY).
+        ``bn_epi`` (``MaskEpi`` / ``ResEpi``) selects a BatchNorm-backward epilogue that also
+        returns Σg, Σg·x̂ partials (segment-major across stride-2 parity classes) → (dx,
+        partial, blocks_per_segment); a ``ResEpi`` with ``ad`` → (p3, pd), the partials of the
+        producer's downsample BN too.
+        ``bnb`` (1x1 stride-1; 3x3 stride-1 on the patch kernel with ``bnb_out``): the A operand
+        is the BatchNorm backward coef.A·dyn + coef.B·a + coef.D computed in the prologue;
+        ``bnb_out`` receives that operand (the weight gradient's dY).
         ``compact`` (stride-2 1x1, pad 0): return the dgrad only at the even input positions, as
         a dense [N, ceil(H/2), ceil(W/2), Ci] tensor (one stride-1 GEMM, no zero fill).
         ``sub_resid``: the residual (``dx`` with ``accumulate``, or bn_epi's resid) is such a
@@ -802,98 +860,63 @@ class FusedStages:
         """
         Nb, H, W, Ci = in_shape
         _, OH, OW, Co = dyn.shape
-        KH = KW = cs.k
         dev = dyn.device
+        if bn_epi is not None:  # (a plain tuple of either layout is taken too)
+            bn_epi = (MaskEpi if bn_epi[0] == "mask" else ResEpi)._make(bn_epi)
         w = shadow_ohwi(cs.conv.weight, Ci)
+        plan = dgrad_plan(Nb, H, W, Ci, OH, OW, Co, cs.k, cs.stride, cs.pad, compact)
+        launches = [(self._dgrad_weight(ops, cs, w, ln), ln) for ln in plan.launches]
         if compact:
-            assert cs.stride == 2 and KH == 1 and cs.pad == 0 and bn_epi is None
-            assert not accumulate and (OH, OW) == ((H + 1) // 2, (W + 1) // 2)
+            assert bn_epi is None and not accumulate
             dc = _empty_nhwc(Nb, OH, OW, Ci, dev)
-            wt = self._dgrad_weight(ops, cs, w, (0, 0), [Co, 1, 1, Ci, 1, 1, 0, 2, 0, 2])
-            g = [Nb, OH, OW, Co, OH, OW, 1, 1, 1, 1, 1, 1, 0, 0, Ci, OH, OW, 1, 1, 0, 0, Ci]
-            v = igemm_choose(ops, dyn, wt, dc, g)
-            igemm_launch(ops, dyn, wt, dc, g, v)
+            (wt, ln), = launches
+            job = Igemm(dyn, wt, dc, ln.geom)
+            job.launch(ops, job.choose(ops))
             return dc, None, 0
         resid_c = None
         if sub_resid:
             assert cs.stride == 1 and (accumulate or bn_epi is not None)
-            resid_c = dx if bn_epi is None else bn_epi[1]
+            resid_c = dx if bn_epi is None else bn_epi.resid
             dx = None  # the full-resolution result is a new tensor
         if dx is None:
             dx = _empty_nhwc(Nb, H, W, Ci, dev)
-        launches = []
-        if cs.stride == 1:
-            wt = self._dgrad_weight(ops, cs, w, (0, 0),
-                                    [Co, KH, KW, Ci, KH, KW, KH - 1, -1, KW - 1, -1])
-            g = [Nb, OH, OW, Co, H, W, KH, KW, 1, 1, 1, 1, -(KH - 1 - cs.pad),
-                 -(KW - 1 - cs.pad), Ci, H, W, 1, 1, 0, 0, Ci]
-            launches.append((wt, g, Nb * H * W))
-        else:
-            assert cs.stride == 2
-            zero_needed = False
-            for r in (0, 1):
-                for c in (0, 1):
-                    kh0, kw0 = (r + cs.pad) % 2, (c + cs.pad) % 2
-                    nkh = (KH - kh0 + 1) // 2 if kh0 < KH else 0
-                    nkw = (KW - kw0 + 1) // 2 if kw0 < KW else 0
-                    ohc, owc = (H - r + 1) // 2, (W - c + 1) // 2
-                    if ohc == 0 or owc == 0:
-                        continue
-                    if nkh == 0 or nkw == 0:
-                        zero_needed = True
-                        continue
-                    wt = self._dgrad_weight(ops, cs, w, (r, c),
-                                            [Co, KH, KW, Ci, nkh, nkw, kh0, 2, kw0, 2])
-                    ih0 = (r + cs.pad - kh0) // 2
-                    iw0 = (c + cs.pad - kw0) // 2
-                    g = [Nb, OH, OW, Co, ohc, owc, nkh, nkw, 1, 1, -1, -1, ih0, iw0, Ci,
-                         H, W, 2, 2, r, c, Ci]
-                    launches.append((wt, g, Nb * ohc * owc))
-            if zero_needed:
-                assert bn_epi is None, "BN-epilogue dgrad needs every output position covered"
-                if not accumulate:
-                    dx.zero_()
+        if plan.zero_fill:
+            assert bn_epi is None, "BN-epilogue dgrad needs every output position covered"
+            if not accumulate:
+                dx.zero_()
         if bn_epi is None:
-            epi = (1, dx, None) if accumulate else None
+            epi = Epilogue(1, dx) if accumulate else None
             if resid_c is not None:
-                epi = (1 | _EPI_SUB, resid_c, None)
-            for wt, g, M in launches:
-                v = igemm_choose(ops, dyn, wt, dx, g, epi=epi)
-                igemm_launch(ops, dyn, wt, dx, g, v, epi=epi)
+                epi = Epilogue(1, resid_c, sub=True)
+            for wt, ln in launches:
+                job = Igemm(dyn, wt, dx, ln.geom, epi=epi)
+                job.launch(ops, job.choose(ops))
             return dx, None, 0
         assert not accumulate
-        if bn_epi[0] == "mask":
-            _, a_prev, bs = bn_epi
-            epi = (3, None, a_prev)
-            tables = (bs.ss.view(-1), bs.mi)
+        if bn_epi.kind == "mask":
+            bs = bn_epi.bs
+            epi = Epilogue(3, b=bn_epi.a_prev, ss=bs.ss.view(-1), mi=bs.mi)
         else:
-            _, resid, mask, a_prev, mi, ad_prev, mid_prev = bn_epi
-            epi = (4 | (_EPI_SUB if resid_c is not None else 0), resid, None, a_prev, mask)
-            tables = (None, mi)
-        chosen = []
+            epi = Epilogue(4, bn_epi.resid, c=bn_epi.a_prev, mask=bn_epi.mask,
+                           sub=resid_c is not None, mi=bn_epi.mi, c2=bn_epi.ad, mi2=bn_epi.mid)
         bpro = None
         if bnb is not None:
             assert cs.stride == 1 and len(launches) == 1 and (cs.k == 1 or bnb_out is not None)
-            SC = S * dyn.shape[-1]
-            c = bnb[1]
-            bpro = (c[:SC], c[SC:2 * SC], c[2 * SC:], launches[0][2] // S, bnb[0])
-        for wt, g, M in launches:
-            seg = M // S
-            v = igemm_choose(ops, dyn, wt, dx, g, want_stats=True, epi=epi, seg_rows=seg,
-                             epi_tables=tables, bnb=bpro, patch_only=bnb_out is not None)
-            chosen.append((wt, g, M, seg, ops.igemm_variant_bm(v), v))
-        seg_blocks = sum(seg // bm for (_, _, _, seg, bm, _) in chosen)
+            a_b, coef_b = bnb
+            bpro = BnBackward.of(coef_b, S * Co, launches[0][1].M // S, a_b, bnb_out)
+        chosen = []
+        for wt, ln in launches:
+            job = Igemm(dyn, wt, dx, ln.geom, want_stats=True, pro=bpro, epi=epi,
+                        seg_rows=ln.M // S)
+            v = job.choose(ops)
+            chosen.append((job, v, job.seg_rows // ops.igemm_variant_bm(v)))
+        seg_blocks = sum(nb for _, _, nb in chosen)
         partial = torch.empty((S * seg_blocks * 2 * Ci,), device=dev, dtype=torch.float32)
-        second, partial2 = None, None
-        if bn_epi[0] == "res" and bn_epi[5] is not None:
-            partial2 = torch.empty_like(partial)
-            second = (bn_epi[5], bn_epi[6], partial2)
+        partial2 = torch.empty_like(partial) if epi.c2 is not None else None
         base = 0
-        for wt, g, M, seg, bm, v in chosen:
-            igemm_launch(ops, dyn, wt, dx, g, v, stats=partial, epi=epi, seg_rows=seg,
-                         epi_tables=tables, remap=(seg_blocks, base), second=second, bnb=bpro,
-                         bnb_out=bnb_out)
-            base += seg // bm
+        for job, v, nb in chosen:
+            job.launch(ops, v, StatsOut(partial, seg_blocks, base, partial2))
+            base += nb
         if partial2 is not None:
             return dx, (partial, partial2), seg_blocks
         return dx, partial, seg_blocks
@@ -901,21 +924,14 @@ class FusedStages:
     # ------------------------------------------------------------------ dgrad weights
     @staticmethod
     def _wt_params(cs: _ConvSpec):
-        """[(parity class, weight_transform params)] of a conv's dgrad: stride 1 → the flipped,
-        transposed kernel; stride 2 → one sub-kernel per (row, col) parity class."""
+        """[(parity class, weight_transform params)] of a conv's dgrad: the (key, wt) projection
+        of its plan (``conv_hip.dgrad_plan``).  The parameters depend on the conv alone, not on
+        the image: any extent with all four parity classes (2 x 2 on) gives them."""
         conv = cs.conv
-        Co, Ci, KH, KW = conv.out_channels, conv.in_channels, cs.k, cs.k
-        if cs.stride == 1:
-            return [((0, 0), [Co, KH, KW, Ci, KH, KW, KH - 1, -1, KW - 1, -1])]
-        out = []
-        for r in (0, 1):
-            for c in (0, 1):
-                kh0, kw0 = (r + cs.pad) % 2, (c + cs.pad) % 2
-                nkh = (KH - kh0 + 1) // 2 if kh0 < KH else 0
-                nkw = (KW - kw0 + 1) // 2 if kw0 < KW else 0
-                if nkh and nkw:
-                    out.append(((r, c), [Co, KH, KW, Ci, nkh, nkw, kh0, 2, kw0, 2]))
-        return out
+        OH = (2 + 2 * cs.pad - cs.k) // cs.stride + 1
+        plan = dgrad_plan(1, 2, 2, conv.in_channels, OH, OH, conv.out_channels, cs.k, cs.stride,
+                          cs.pad)
+        return [(ln.key, ln.wt) for ln in plan.launches]
 
     def prepare_backward(self, ops) -> None:
         """Transform every conv's dgrad weights in ONE launch (weights change only at the
@@ -937,8 +953,7 @@ class FusedStages:
             Ws, Wts, params, cache = [], [], [], {}
             for cs, w in zip(convs, shadows):
                 for key, p in self._wt_params(cs):
-                    wt = torch.empty((p[3], p[4], p[5], p[0]), device=w.device,
-                                     dtype=torch.bfloat16)
+                    wt = torch.empty(wt_shape(p), device=w.device, dtype=torch.bfloat16)
                     Ws.append(w)
                     Wts.append(wt)
                     params.extend(p)
@@ -969,13 +984,16 @@ class FusedStages:
             ev.record(self._side)
             self._wt_event = ev
 
-    def _dgrad_weight(self, ops, cs: _ConvSpec, w, key, p):
+    def _dgrad_weight(self, ops, cs: _ConvSpec, w, ln: DgradLaunch):
+        """The transformed weight of one dgrad launch: from the batched transform
+        (prepare_backward) when it ran, else transformed here."""
+        shape = ln.wt_shape
         if getattr(self, "_wt_ready", False):
-            wt = self._wt_cache.get((id(cs.conv), key))
-            if wt is not None and wt.shape[0] == p[3]:
+            wt = self._wt_cache.get((id(cs.conv), ln.key))
+            if wt is not None and wt.shape[0] == shape[0]:
                 return wt
-        wt = torch.empty((p[3], p[4], p[5], p[0]), device=w.device, dtype=torch.bfloat16)
-        ops.weight_transform(w, wt, p)
+        wt = torch.empty(shape, device=w.device, dtype=torch.bfloat16)
+        ops.weight_transform(w, wt, ln.wt)
         return wt
 
     # ------------------------------------------------------------------ forward / backward
@@ -988,7 +1006,7 @@ class FusedStages:
         x = xn
         self._prefetch_dgrad_weights(ops, xn)
         br = self._branch_stream(xn)
-        pend = None  # the previous block's output, not yet formed: (aL, ss, res, rss, out, mask)
+        pend = None  # the previous block's output, not yet formed (BlockOutput)
         for b in self.blocks:
             tp = _BlockTape(x=x)
             pro_ss = None
@@ -1044,9 +1062,9 @@ class FusedStages:
                     torch.cuda.current_stream(x.device).wait_stream(br)  # join
                 else:
                     self._down_fwd(ops, b, tp, x, S, st)
-                pend = (aL, bsL.ss, tp.ad, tp.bnd.ss, out, mask)
+                pend = BlockOutput(aL, bsL.ss, tp.ad, tp.bnd.ss, out, mask)
             else:
-                pend = (aL, bsL.ss, x, None, out, mask)
+                pend = BlockOutput(aL, bsL.ss, x, None, out, mask)
             tp.out = out
             tp.mask = mask
             tapes.append(tp)
@@ -1085,11 +1103,10 @@ class FusedStages:
         out, tapes = self.forward(x0)
         return out, tapes, tp
 
-    def _out_apply(self, ops, pend, S: int) -> None:
+    def _out_apply(self, ops, pend: BlockOutput, S: int) -> None:
         """Block output = relu(bn3(aL) + shortcut) and its ReLU bitmask, as its own pass."""
-        aL, ss, res, rss, out, mask = pend
         self.out_apply_calls += 1
-        ops.bn_apply_ss(aL, ss, res, rss, out, S, True, mask)
+        ops.bn_apply_ss(pend.aL, pend.ss, pend.res, pend.rss, pend.out, S, True, pend.mask)
 
     def _branch_stream(self, t: torch.Tensor):
         if not (getattr(self, "branch_stream", False) and t.is_cuda):
@@ -1169,8 +1186,8 @@ class FusedStages:
             _ext.TAG = "stem wgrad"
             # on the main stream: nothing else is left for it, while the weight-gradient stream
             # still works through layer1.0's (the tail of the step runs both side by side)
-            self._wgrad(ops, g, stem_tape.x, self.stem, None, S, bnb=(stem_tape.acts[0], coef),
-                        main=True)
+            self._wgrad(ops, g, stem_tape.x, self.stem, None, S,
+                        bnb=LazyBN(stem_tape.acts[0], coef), main=True)
             _ext.TAG = ""
             g = None
         if main is not None:
@@ -1223,7 +1240,7 @@ class FusedStages:
             coefL = self._bn_bwd_finish(ops, h3, S)
             if hd is None:
                 if L > 0 and self._bnb_ok(b.convs[L], aL, S):
-                    lazy = (aL, coefL)  # da never materialised: conv L's operand prologues
+                    lazy = LazyBN(aL, coefL)  # da never materialised: conv L's operand prologues
                 else:
                     ops.bn_bwd_apply(g3, None, aL, coefL, S, False, da, None)
         dad = None
@@ -1236,7 +1253,7 @@ class FusedStages:
                 # with BN3's backward left to conv3's operand prologues
                 coefd = self._bn_bwd_finish(ops, hd, S)
                 if self._lazy_bn3_ds_ok(b, tp, aL, S):
-                    lazy = (aL, coefL)
+                    lazy = LazyBN(aL, coefL)
                     if self._ds_dual_ok(b, tp, S):
                         ds_dual = (g3, coefd)  # dad never materialised
                     else:
@@ -1277,7 +1294,7 @@ class FusedStages:
         # conv chain, last to first: dgrad (+ BN-bwd partials) → start BN all-reduce → wgrad →
         # finish BN → apply
         lazy0 = None
-        pend = None  # (g, a, coef): the BN backward feeding conv i, left to its patch dgrad
+        pend = None  # (g, LazyBN): the BN backward feeding conv i, left to its patch dgrad
         for i in range(L, 0, -1):
             cs = b.convs[i]
             xin, pro_ss = tp.ins[i]
@@ -1287,12 +1304,12 @@ class FusedStages:
             if pend is not None:
                 # dgrad with the BN backward in its patch prologue; that operand is stored as
                 # the weight gradient's dY on the way (no separate bn_bwd_apply pass)
-                gsrc, a_b, coef_b = pend
+                gsrc, lazy_b = pend
                 pend = None
-                dy_m = torch.empty_like(a_b)
+                dy_m = torch.empty_like(lazy_b.a)
                 gm, part, nb = self._dgrad(ops, gsrc, cs, a_prev.shape, S,
-                                           bn_epi=("mask", a_prev, bs_prev), bnb=(a_b, coef_b),
-                                           bnb_out=dy_m)
+                                           bn_epi=MaskEpi("mask", a_prev, bs_prev),
+                                           bnb=lazy_b, bnb_out=dy_m)
                 h = self._bn_bwd_start(ops, b.convs[i - 1].bn, part, nb, bs_prev, S, st)
                 _ext.TAG = f"{b.name} conv{i + 1} wgrad"
                 self._wgrad(ops, dy_m, xin, cs, pro_ss, S)
@@ -1302,18 +1319,18 @@ class FusedStages:
                 h = self._bn_bwd_start(ops, b.convs[i - 1].bn, part, nb, bs_prev, S, st)
             else:
                 gm, part, nb = self._dgrad(ops, dyn, cs, a_prev.shape, S,
-                                           bn_epi=("mask", a_prev, bs_prev), bnb=bnb)
+                                           bn_epi=MaskEpi("mask", a_prev, bs_prev), bnb=bnb)
                 h = self._bn_bwd_start(ops, b.convs[i - 1].bn, part, nb, bs_prev, S, st)
                 _ext.TAG = f"{b.name} conv{i + 1} wgrad"
                 self._wgrad(ops, dyn, xin, cs, pro_ss, S, bnb=bnb)
             _ext.TAG = f"{b.name} bn{i} bwd"
             coef = self._bn_bwd_finish(ops, h, S)
             if i == 1 and prev is not None and self._lazy_bn1_ok(b, a_prev, S):
-                lazy0 = (a_prev, coef)  # da1 never materialised: conv1's operand prologues
+                lazy0 = LazyBN(a_prev, coef)  # da1 never materialised: conv1's prologues
                 da = gm
                 continue
             if i - 1 >= 1 and self._patch_bnb_ok(ops, b.convs[i - 1], a_prev, S):
-                pend = (gm, a_prev, coef)
+                pend = (gm, LazyBN(a_prev, coef))
                 continue
             da_next = torch.empty_like(a_prev)
             ops.bn_bwd_apply(gm, None, a_prev, coef, S, False, da_next, None)
@@ -1339,9 +1356,9 @@ class FusedStages:
             dx, part, nb = self._dgrad(ops, da, cs0, tp.x.shape, S, bnb=lazy0,
                                        dx=resid if b.down is not None and not compact else None,
                                        sub_resid=compact,
-                                       bn_epi=("res", resid, ptp.mask, ptp.acts[-1],
-                                               ptp.bns[-1].mi, ptp.ad if pds else None,
-                                               ptp.bnd.mi if pds else None))
+                                       bn_epi=ResEpi("res", resid, ptp.mask, ptp.acts[-1],
+                                                     ptp.bns[-1].mi, ptp.ad if pds else None,
+                                                     ptp.bnd.mi if pds else None))
             if pds:
                 p3, pd = part
                 h = (self._bn_bwd_start(ops, pb.convs[-1].bn, p3, nb, ptp.bns[-1], S, st),

@@ -35,12 +35,9 @@ from typing import Optional
 import torch
 
 from ..ops import _ext
-from ..ops.conv_hip import igemm_choose, igemm_launch
+from ..ops.conv_hip import (BnApply, BnBackward, Epilogue, Igemm, StatsOut, WgradDY, WgradX,
+                            gemm_geom, run_wgrad)
 from ..parallel import state as pstate
-
-
-def _geom(M, K, N):
-    return [M, 1, 1, K, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, N, 1, 1, 1, 1, 0, 0, N]
 
 
 def _w16(weight: torch.Tensor) -> torch.Tensor:
@@ -58,25 +55,8 @@ def _bnops():
 def _wgrad_direct(ops, dY, X, out, geom, creal, pro=None, dpro=None):
     """Weight gradient in ONE split written straight into ``out`` (no split-reduction launch):
     the head's GEMMs have 1,024 rows, so the 128 x 128 output tiles already give up to 256
-    blocks.  ``pro = (sc, sh, seg_rows, relu, S)``: X-operand BN + ReLU; ``dpro = (dY2, coef,
-    seg_rows, S)``: dY-operand BatchNorm backward (register-staged variants, which take the
-    per-row view segment)."""
-    from ..ops import tuning
-    psc, psh, pseg, prelu, pS = pro if pro is not None else (None, None, 0, False, 1)
-    dY2, dcoef, dseg, dS = dpro if dpro is not None else (None, None, 0, 1)
-    key = ("wgrad1split", tuple(geom), creal, psc is not None, dpro is not None)
-
-    def launch(v, o):
-        ops.wgrad(dY, X, o, o, geom, 1, creal, 0.0, psc, psh, pseg, prelu, pS, v, dY2, dcoef,
-                  dseg, dS)
-
-    v = tuning.cached(key)
-    if v is None:
-        cands = [v for v in range(ops.wgrad_nvariants())
-                 if ops.wgrad_variant_ok(v, geom, psc is not None, dpro is not None)
-                 and (dpro is None or not ops.wgrad_variant_glds(v))]
-        v = tuning.pick(key, cands, 0, lambda vv: launch(vv, torch.empty_like(out)))
-    launch(v, out)
+    blocks."""
+    run_wgrad(ops, dY, X, out, geom, creal, pro=pro, dpro=dpro, one_split=True)
 
 
 def _deliver(param: torch.Tensor, compute) -> Optional[torch.Tensor]:
@@ -153,8 +133,8 @@ def _gemm2_pregather(ops, st, y1, W2, z, v2, bias2, bs, S: int, seg: int, H: int
             p2 = torch.empty((ks * seg * D,), device=dev, dtype=torch.float32)
             ops.gemm_sk(y1[rows], W2.view(D, H), sc, sh, seg, ks, p2, bias2, zv)
         else:
-            igemm_launch(ops, y1[rows], W2, zv, _geom(seg, H, D), v2, bias=bias2,
-                         pro=(sc, sh, seg, True))
+            Igemm(y1[rows], W2, zv, gemm_geom(seg, H, D), bias2,
+                  pro=BnApply(sc, sh, seg)).launch(ops, v2)
         tmp = torch.empty((W * seg, D), device=dev, dtype=torch.bfloat16)
         side.wait_stream(cur)
         with torch.cuda.stream(side):
@@ -185,19 +165,19 @@ class MLPHeadFn(torch.autograd.Function):
         W1, W2 = _w16(lin1.weight), _w16(lin2.weight)
         # GEMM 1: bias + BatchNorm statistics partials
         y1 = torch.empty((M, H), device=dev, dtype=torch.bfloat16)
-        g1 = _geom(M, K, H)
         bias1 = b1.detach().float().contiguous()
-        v = igemm_choose(ops, xc, W1, y1, g1, bias=bias1, want_stats=True, seg_rows=seg)
+        gemm1 = Igemm(xc, W1, y1, gemm_geom(M, K, H), bias1, want_stats=True, seg_rows=seg)
+        v = gemm1.choose(ops)
         bm = ops.igemm_variant_bm(v)
         part = torch.empty(((M // bm) * 2 * H,), device=dev, dtype=torch.float32)
-        igemm_launch(ops, xc, W1, y1, g1, v, bias=bias1, stats=part)
+        gemm1.launch(ops, v, StatsOut(part))
         bs = _bnops()._bn_fwd(ops, bn, part, seg // bm, seg, S, st)
         # GEMM 2 on relu(bn(y1)) formed in the operand prologue
         z = torch.empty((M, D), device=dev, dtype=torch.bfloat16)
-        g2 = _geom(M, H, D)
-        pro = (bs.ss[0], bs.ss[1], seg, True)
         bias2 = b2.detach().float().contiguous() if b2 is not None else None
-        v2 = igemm_choose(ops, y1, W2, z, g2, bias=bias2, pro=pro, seg_rows=seg)
+        gemm2 = Igemm(y1, W2, z, gemm_geom(M, H, D), bias2,
+                      pro=BnApply(bs.ss[0], bs.ss[1], seg), seg_rows=seg)
+        v2 = gemm2.choose(ops)
         if _pregather_ok(mod, st, S, seg, D):
             _gemm2_pregather(ops, st, y1, W2, z, v2, bias2, bs, S, seg, H, D)
         elif _splitk_ok(M, H, D):
@@ -206,7 +186,7 @@ class MLPHeadFn(torch.autograd.Function):
             part2 = torch.empty((ks * M * D,), device=dev, dtype=torch.float32)
             ops.gemm_sk(y1, W2.view(D, H), bs.ss[0], bs.ss[1], seg, ks, part2, bias2, z)
         else:
-            igemm_launch(ops, y1, W2, z, g2, v2, bias=bias2, pro=pro)
+            gemm2.launch(ops, v2)
         # the backward's transposed weights, one batched launch (weights are final until the
         # optimizer step, which comes after the backward)
         wt1, wt2 = _transposed(ops, mod, W1, W2, K, H, D)
@@ -237,37 +217,32 @@ class MLPHeadFn(torch.autograd.Function):
         bnx = _bnops()
         # dgrad 2: g = (dz·W2)·[bn(y1) > 0] with the BN-backward partials Σg, Σg·x̂
         gm = torch.empty((M, H), device=dev, dtype=torch.bfloat16)
-        gd = _geom(M, D, H)
-        epi = (3, None, y1)
-        tables = (bs.ss.view(-1), bs.mi)
-        v = igemm_choose(ops, dzc, wt2, gm, gd, want_stats=True, epi=epi, seg_rows=seg,
-                         epi_tables=tables)
+        dgrad2 = Igemm(dzc, wt2, gm, gemm_geom(M, D, H), want_stats=True,
+                       epi=Epilogue(3, b=y1, ss=bs.ss.view(-1), mi=bs.mi), seg_rows=seg)
+        v = dgrad2.choose(ops)
         nb = seg // ops.igemm_variant_bm(v)
         part = torch.empty((S * nb * 2 * H,), device=dev, dtype=torch.float32)
-        igemm_launch(ops, dzc, wt2, gm, gd, v, stats=part, epi=epi, seg_rows=seg,
-                     epi_tables=tables, remap=(nb, 0))
+        dgrad2.launch(ops, v, StatsOut(part, seg_blocks=nb))
         h = bnx._bn_bwd_start(ops, bn, part, nb, bs, S, st)
         # dW2 = dzᵀ · relu(bn(y1)) (X prologue), independent of the BN backward
-        pro = (bs.ss[0], bs.ss[1], seg, True, S)
+        pro = WgradX(bs.ss[0], bs.ss[1], seg, True, S)
         gw2 = _deliver(lin2.weight, lambda o: _wgrad_direct(ops, dzc, y1, o.view(D, 1, 1, H),
-                                                            _geom(M, H, D), H, pro=pro))
+                                                            gemm_geom(M, H, D), H, pro=pro))
         gb2 = None
         if ctx.has_b2:
             gb2 = _deliver(lin2.bias, lambda o: ops.colsum(dzc, o, 0.0))
         coef = bnx._bn_bwd_finish(ops, h, S)
         # dgrad 1 with the BN backward da = A·g + B·y1 + D in the A-operand prologue
-        SC = S * H
-        bpro = (coef[:SC], coef[SC:2 * SC], coef[2 * SC:], seg, y1)
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty((M, K), device=dev, dtype=torch.bfloat16)
-            gx = _geom(M, H, K)
-            v = igemm_choose(ops, gm, wt1, dx, gx, bnb=bpro)
-            igemm_launch(ops, gm, wt1, dx, gx, v, bnb=bpro)
+            dgrad1 = Igemm(gm, wt1, dx, gemm_geom(M, H, K),
+                           pro=BnBackward.of(coef, S * H, seg, y1))
+            dgrad1.launch(ops, dgrad1.choose(ops))
         # dW1 = daᵀ · x, the same prologue on the dY operand
         gw1 = _deliver(lin1.weight, lambda o: _wgrad_direct(ops, gm, xc, o.view(H, 1, 1, K),
-                                                            _geom(M, K, H), K,
-                                                            dpro=(y1, coef, seg, S)))
+                                                            gemm_geom(M, K, H), K,
+                                                            dpro=WgradDY(y1, coef, seg, S)))
         gb1 = _zero_bias_grad(mod, lin1.bias)
         return dx, gw1, gb1, None, None, gw2, gb2, None, None
 

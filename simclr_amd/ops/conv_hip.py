@@ -17,130 +17,328 @@ one row of the descriptor tables in ``csrc/conv.hip``):
               stride-1 sub-convolution with negative tap step (dh = −1) whose outputs land on
               rows 2i+r, cols 2j+c (strided epilogue).  No zero-inserted MACs.
 * wgrad     : dW[co][kh][kw][ci] = Σ_m dy[m][co] · im2col(x)[m][(kh,kw,ci)], split over m.
+
+How a launch is described (the fused executor and the fused head build the same records):
+
+* ``Geom``: the kernels' ``ConvGeom`` by field name (``fwd_geom``, ``gemm_geom``, and the dgrad
+  geometries of ``dgrad_plan``); the ops take it as their ``int[] geom``.
+* ``dgrad_plan``: the dgrad decomposition above, once — per launch the parity class, the
+  ``weight_transform`` parameters of its B operand, the ``Geom`` and the row count, plus whether
+  dx needs a zero fill; also the compact stride-2 1x1 form.
+* ``Igemm``: one implicit GEMM — operands, ``Geom``, at most one A-operand prologue (``BnApply``,
+  ``BnBackward``, ``BlockOut``), an ``Epilogue``, the segment rows.  ``choose`` (tuning key,
+  admissibility, trials on scratch outputs) and ``launch`` (with a ``StatsOut``) read the same
+  fields and share the one ``ops.igemm`` call.
+* ``run_wgrad``: the one ``ops.wgrad`` call, with the ``WgradX`` / ``WgradDY`` operand prologues;
+  split over M, or ``one_split`` straight into the output.
 """
 from __future__ import annotations
 
-import os
-from typing import Optional, Tuple
+import functools
+from typing import NamedTuple, Optional, Tuple, Union
 
 import torch
 
 from . import _ext, tuning
 
 
-def igemm_choose(ops, A, B, out, geom, bias=None, want_stats=False, pro=None, epi=None,
-                 seg_rows: int = 0, epi_tables=None, bnb=None, dual=None,
-                 patch_only: bool = False) -> int:
-    """Autotuned tile variant for this problem (admissible: BM divides the segment rows /
-    M whenever per-segment prologue, statistics or the mode-3 epilogue need block-uniform
-    segments).  ``dual = (res, rss, out, mask)``: block-output prologue (see igemm_launch)."""
-    M = geom[0] * geom[4] * geom[5]
-    N = geom[14]
-    psc, psh, pseg, prelu = pro if pro is not None else (None, None, 0, False)
-    pd, A2 = None, None
-    if bnb is not None:  # BN-backward prologue: a = coefA·A + coefB·A2 + coefD
-        psc, psh, pd, pseg, A2 = bnb
-    rss, pout, pmask = None, None, None
-    if dual is not None:
-        A2, rss, pout, pmask = dual
-    emode, ea, eb = epi[:3] if epi is not None else (0, None, None)
-    ess, emi = epi_tables if epi_tables is not None else (None, None)
-    key = ("igemm", tuple(geom), want_stats, psc is not None, emode, bias is not None, seg_rows,
-           bnb is not None, dual is not None, patch_only)
-    hit = tuning.cached(key)
-    if hit is not None:  # steady state: no per-launch walk over the variant table
-        return hit
-    cands = []
-    for v in range(ops.igemm_nvariants()):
-        bm = ops.igemm_variant_bm(v)
-        if dual is not None:
-            if not ops.igemm_dual_ok(v, geom):
+def _pair(v):
+    return (v, v) if isinstance(v, int) else tuple(v)
+
+
+_GEOM_FIELDS = ("Nb IH IW C OH OW KH KW ish isw dh dw ih0 iw0 N OHp OWp osh osw ooh oow "
+                "ldo").split()
+
+
+class Geom(NamedTuple("Geom", [(f, int) for f in _GEOM_FIELDS])):
+    """Geometry of one implicit-GEMM / weight-gradient launch: ``ConvGeom`` of
+    ``csrc/kernels.h``, field for field.  It *is* the 22-int tuple the ops take as ``int[] geom``
+    (and compares / hashes like it, so tuning keys built from it match recorded tables)."""
+    __slots__ = ()
+
+    @property
+    def M(self) -> int:
+        """GEMM rows: output positions gathered by this launch."""
+        return self.Nb * self.OH * self.OW
+
+    @property
+    def K(self) -> int:
+        return self.KH * self.KW * self.C
+
+
+@functools.lru_cache(maxsize=None)
+def _geom(Nb, IH, IW, C, OH, OW, KH, KW, N, ih0=0, iw0=0, stride=1, step=1, full=None,
+          ostride=1, ooh=0, oow=0) -> Geom:
+    """``stride``: input stride; ``step``: tap step (-1: taps walk backwards); the output
+    rows land in a ``full`` = (OHp, OWp) image at ``ostride * i + (ooh, oow)``."""
+    OHp, OWp = full if full is not None else (OH, OW)
+    return Geom(Nb, IH, IW, C, OH, OW, KH, KW, stride, stride, step, step, ih0, iw0, N,
+                OHp, OWp, ostride, ostride, ooh, oow, N)
+
+
+def fwd_geom(N, H, W, C, OH, OW, KH, KW, stride, pad, Co) -> Geom:
+    return _geom(N, H, W, C, OH, OW, KH, KW, Co, ih0=-pad, iw0=-pad, stride=stride)
+
+
+def gemm_geom(M, K, N) -> Geom:
+    """A dense [M, K] x [N, K]ᵀ GEMM: a 1x1 conv over an [M, 1, 1, K] "image"."""
+    return _geom(M, 1, 1, K, 1, 1, 1, 1, N)
+
+
+def wt_shape(p):
+    """Shape [Ci][kh][kw][Co] of the weight that ``weight_transform`` parameters ``p`` give."""
+    return (p[3], p[4], p[5], p[0])
+
+
+class DgradLaunch(NamedTuple):
+    key: Tuple[int, int]          # output parity class (r, c); (0, 0) for a one-launch dgrad
+    wt: Tuple[int, ...]           # the 10 weight_transform parameters of its B operand
+    geom: Geom
+    M: int                        # its GEMM rows
+
+    @property
+    def wt_shape(self):
+        return wt_shape(self.wt)
+
+
+class DgradPlan(NamedTuple):
+    launches: Tuple[DgradLaunch, ...]
+    zero_fill: bool               # some input positions get no tap: dx must be zeroed first
+
+
+@functools.lru_cache(maxsize=None)
+def dgrad_plan(Nb, H, W, Ci, OH, OW, Co, k, stride, pad, compact: bool = False) -> DgradPlan:
+    """The ordered launches of the input gradient dx [Nb, H, W, Ci] of a k x k conv from
+    dy [Nb, OH, OW, Co] (the decomposition of the module docstring; ``k``: int or (KH, KW)).
+
+    ``compact`` (stride-2 1x1 unpadded): only the even input positions, as a dense
+    [Nb, OH, OW, Ci] tensor — the (0, 0) parity class as one stride-1 GEMM, no zero fill."""
+    KH, KW = _pair(k)
+    if compact:
+        assert stride == 2 and KH == KW == 1 and pad == 0
+        assert (OH, OW) == ((H + 1) // 2, (W + 1) // 2)
+        return DgradPlan((DgradLaunch((0, 0), (Co, 1, 1, Ci, 1, 1, 0, 2, 0, 2),
+                                      _geom(Nb, OH, OW, Co, OH, OW, 1, 1, Ci), Nb * OH * OW),),
+                         False)
+    if stride == 1:
+        g = _geom(Nb, OH, OW, Co, H, W, KH, KW, Ci, ih0=-(KH - 1 - pad), iw0=-(KW - 1 - pad))
+        return DgradPlan((DgradLaunch((0, 0), (Co, KH, KW, Ci, KH, KW, KH - 1, -1, KW - 1, -1),
+                                      g, Nb * H * W),), False)
+    assert stride == 2, "only stride 1/2 convolutions are supported"
+    launches, zero_fill = [], False
+    for r in (0, 1):
+        for c in (0, 1):
+            kh0, kw0 = (r + pad) % 2, (c + pad) % 2
+            nkh = (KH - kh0 + 1) // 2 if kh0 < KH else 0
+            nkw = (KW - kw0 + 1) // 2 if kw0 < KW else 0
+            ohc, owc = (H - r + 1) // 2, (W - c + 1) // 2
+            if ohc == 0 or owc == 0:
                 continue
-        elif not ops.igemm_variant_ok(v, geom, psc is not None, bnb is not None, emode):
-            continue  # e.g. LDS-DMA variants: C % 64 == 0, BN-apply prologue only on 1x1
-        if want_stats and M % bm:
-            continue
-        if psc is not None and pseg % bm:
-            continue
-        if seg_rows and seg_rows % bm:
-            continue
-        if patch_only and not ops.igemm_variant_patch(v):
-            continue  # (the materialised BN-backward operand exists only in the patch kernel)
-        cands.append(v)
-    if not cands:
-        raise ValueError(f"no igemm tile variant admissible for M={M} segment rows "
-                         f"{seg_rows or pseg}")
-    default = 1 if N <= 64 else 0
-    if default not in cands:
-        default = cands[0]
-    ec = epi[3] if epi is not None and len(epi) > 3 else None
-    em = epi[4] if epi is not None and len(epi) > 4 else None
-
-    def trial(v):
-        bm = ops.igemm_variant_bm(v)
-        st = (torch.empty(((M + bm - 1) // bm) * 2 * N, device=out.device, dtype=torch.float32)
-              if want_stats else None)
-        # every output of a trial is scratch (tuning.py: trials touch no live tensor), the
-        # block-output prologue's out / mask included
-        tout = torch.empty_like(pout) if pout is not None else None
-        tmask = torch.empty_like(pmask) if pmask is not None else None
-        ops.igemm(A, B, torch.empty_like(out), bias, st, geom, psc, psh, pseg, prelu, emode, ea,
-                  eb, v, ess, emi, seg_rows, 0, 0, ec, em, None, None, None, pd, A2, rss, tout,
-                  tmask)
-
-    return tuning.pick(key, cands, default, trial)
+            if nkh == 0 or nkw == 0:
+                zero_fill = True
+                continue
+            g = _geom(Nb, OH, OW, Co, ohc, owc, nkh, nkw, Ci, ih0=(r + pad - kh0) // 2,
+                      iw0=(c + pad - kw0) // 2, step=-1, full=(H, W), ostride=2, ooh=r, oow=c)
+            launches.append(DgradLaunch((r, c), (Co, KH, KW, Ci, nkh, nkw, kh0, 2, kw0, 2), g,
+                                        Nb * ohc * owc))
+    return DgradPlan(tuple(launches), zero_fill)
 
 
-def igemm_launch(ops, A, B, out, geom, v, bias=None, stats=None, pro=None, epi=None,
-                 seg_rows: int = 0, epi_tables=None, remap=(0, 0), second=None,
-                 bnb=None, dual=None, bnb_out=None) -> None:
-    """``second = (c2, mi2, stats2)``: mode-4 second BatchNorm stream (see conv.hip);
-    ``bnb = (coefA, coefB, coefD, seg_rows, A2)``: BatchNorm-backward A-operand prologue;
-    ``dual = (res, rss, out, mask)``: block-output prologue — A is a block's pre-BN conv3
-    activation, ``pro`` its BN scale/shift, ``res`` the residual (``rss`` its BN [2][S][C] table
-    or None for identity); the conv consumes relu(bn(A) + res') and also writes it to ``out``
-    with its ReLU bitmask ``mask``.  ``bnb_out``: with ``bnb`` on a patch variant, the
-    BatchNorm-backward operand is also written there (the weight gradient's dY)."""
-    psc, psh, pseg, prelu = pro if pro is not None else (None, None, 0, False)
-    pd, A2 = None, None
-    if bnb is not None:
-        psc, psh, pd, pseg, A2 = bnb
-    rss, pout, pmask = None, None, None
-    if dual is not None:
-        A2, rss, pout, pmask = dual
-    if bnb_out is not None:  # patch kernels: the BN-backward operand also stored (wgrad's dY)
-        pout = bnb_out
-    emode, ea, eb = epi[:3] if epi is not None else (0, None, None)
-    ec = epi[3] if epi is not None and len(epi) > 3 else None
-    em = epi[4] if epi is not None and len(epi) > 4 else None
-    ess, emi = epi_tables if epi_tables is not None else (None, None)
-    c2, mi2, st2 = second if second is not None else (None, None, None)
-    ops.igemm(A, B, out, bias, stats, geom, psc, psh, pseg, prelu, emode, ea, eb, v, ess, emi,
-              seg_rows, remap[0], remap[1], ec, em, c2, mi2, st2, pd, A2, rss, pout, pmask)
+# ---------------------------------------------------------------------------- fusion operands
+# A-operand prologues of the implicit GEMM.  The three kinds share the kernel's operand slots
+# (sc, sh, d, seg_rows, relu, A2, rss, out, mask); each record names the ones it owns and
+# leaves the others at the class-level None.
+
+class BnApply(NamedTuple):
+    """a = relu?(sc[seg]·A + sh[seg]): the previous BatchNorm (+ ReLU) applied on the gathered
+    operand; ``sc`` / ``sh`` are [S][C], ``seg_rows`` the rows per view segment."""
+    sc: Optional[torch.Tensor]
+    sh: Optional[torch.Tensor]
+    seg_rows: int
+    relu: bool = True
+    d = A2 = rss = out = mask = None
 
 
-def run_igemm(ops, A, B, out, geom, bias=None, want_stats=False, pro=None, epi=None):
-    """Launch the implicit GEMM with the autotuned tile variant for this problem.
+class BnBackward(NamedTuple):
+    """a = sc[seg]·A + sh[seg]·A2 + d[seg]: the BatchNorm backward (coefficient rows A, B, D of
+    ``coef`` [3][S][C]) of the output gradient A against the pre-BN activation ``A2``.  ``out``
+    (patch variants only): the operand is also stored there — the weight gradient's dY."""
+    sc: torch.Tensor
+    sh: torch.Tensor
+    d: torch.Tensor
+    seg_rows: int
+    A2: torch.Tensor
+    out: Optional[torch.Tensor] = None
+    relu = False
+    rss = mask = None
 
-    pro = (scale[S][C], shift[S][C], rows_per_segment, relu) applies the previous BatchNorm on the
-    A operand; epi = (mode, a, b) accumulates into the output.  Returns (stats, nblk) or None."""
-    M = geom[0] * geom[4] * geom[5]
-    N = geom[14]
+    @classmethod
+    def of(cls, coef, SC: int, seg_rows: int, A2, out=None) -> "BnBackward":
+        """From the flat ``coef`` [3][S][C] of ``bn_bwd_finalize`` (``SC`` = S·C)."""
+        return cls(coef[:SC], coef[SC:2 * SC], coef[2 * SC:], seg_rows, A2, out)
+
+
+class BlockOut(NamedTuple):
+    """a = relu(sc[seg]·A + sh[seg] + res'): A is a residual block's pre-BN last activation,
+    ``res`` its residual (``rss``: the residual's BN [2][S][C] table, None for identity); the
+    conv consumes the block output and also writes it to ``out`` with its ReLU bitmask
+    ``mask``."""
+    sc: torch.Tensor
+    sh: torch.Tensor
+    seg_rows: int
+    res: torch.Tensor
+    rss: Optional[torch.Tensor]
+    out: torch.Tensor
+    mask: torch.Tensor
+    relu = True
+    d = None
+    A2 = property(lambda self: self.res)
+
+
+_NO_PRO = BnApply(None, None, 0, False)
+
+
+class Epilogue(NamedTuple):
+    """Output epilogue ``mode`` (conv.hip): 1 / 2 accumulate ``a`` (, ``b``) into the output;
+    3 masks with [bn(b) > 0] from the tables ``ss`` / ``mi``; 4 adds the residual ``a`` and
+    masks with the bitmask ``mask``, statistics against ``c`` / ``mi``, and with ``c2`` /
+    ``mi2`` a second BatchNorm's statistics too (``StatsOut.stats2``).  ``sub``: the residual
+    ``a`` is stride-2 subsampled (added at the even positions)."""
+    mode: int = 0
+    a: Optional[torch.Tensor] = None
+    b: Optional[torch.Tensor] = None
+    c: Optional[torch.Tensor] = None
+    mask: Optional[torch.Tensor] = None
+    sub: bool = False
+    ss: Optional[torch.Tensor] = None
+    mi: Optional[torch.Tensor] = None
+    c2: Optional[torch.Tensor] = None
+    mi2: Optional[torch.Tensor] = None
+
+    @property
+    def kernel_mode(self) -> int:
+        return self.mode | 256 if self.sub else self.mode  # bit 8: subsampled residual
+
+
+_NO_EPI = Epilogue()
+
+
+class StatsOut(NamedTuple):
+    """Where a launch's per-block statistics partials go.  ``seg_blocks`` / ``base`` remap them
+    segment-major when several launches (parity classes) share ``stats``: blocks per segment
+    over all of them, and this launch's first block within a segment."""
+    stats: Optional[torch.Tensor] = None
+    seg_blocks: int = 0
+    base: int = 0
+    stats2: Optional[torch.Tensor] = None
+
+
+_NO_STATS = StatsOut()
+
+
+class Igemm(NamedTuple):
+    """One implicit-GEMM launch: operands, geometry and fusions.  ``choose`` picks its tile
+    variant (tuning key, admissibility, trials), ``launch`` issues it; both read these fields.
+    ``seg_rows``: rows per view segment of the output — tiles must not straddle it (per-segment
+    statistics, epilogue tables)."""
+    A: torch.Tensor
+    B: torch.Tensor
+    out: torch.Tensor
+    geom: Geom
+    bias: Optional[torch.Tensor] = None
+    want_stats: bool = False
+    pro: Union[None, BnApply, BnBackward, BlockOut] = None
+    epi: Optional[Epilogue] = None
+    seg_rows: int = 0
+
+    def _issue(self, ops, v, out, so: StatsOut, pro_out, pro_mask) -> None:
+        pro, epi = self.pro or _NO_PRO, self.epi or _NO_EPI
+        ops.igemm(self.A, self.B, out, self.bias, so.stats, self.geom,
+                  pro_sc=pro.sc, pro_sh=pro.sh, pro_seg_rows=pro.seg_rows, pro_relu=pro.relu,
+                  epi_mode=epi.kernel_mode, epi_a=epi.a, epi_b=epi.b, variant=v,
+                  epi_ss=epi.ss, epi_mi=epi.mi,
+                  # the kernel reads the segment only for the epilogue tables / stats remap
+                  seg_rows=self.seg_rows if epi.mi is not None else 0,
+                  stats_seg_blocks=so.seg_blocks, stats_base=so.base, epi_c=epi.c,
+                  epi_mask=epi.mask, epi_c2=epi.c2 if so.stats2 is not None else None,
+                  epi_mi2=epi.mi2 if so.stats2 is not None else None, stats2=so.stats2,
+                  pro_d=pro.d, A2=pro.A2, pro_rss=pro.rss, pro_out=pro_out, pro_mask=pro_mask)
+
+    def choose(self, ops) -> int:
+        """Autotuned tile variant (admissible: BM divides the segment rows / M whenever a
+        per-segment prologue, statistics or a per-segment epilogue need block-uniform
+        segments)."""
+        geom, pro = self.geom, self.pro
+        bnb, dual = type(pro) is BnBackward, type(pro) is BlockOut
+        patch_only = bnb and pro.out is not None  # (that store exists only in the patch kernel)
+        emode = (self.epi or _NO_EPI).kernel_mode
+        key = ("igemm", tuple(geom), self.want_stats, pro is not None, emode,
+               self.bias is not None, self.seg_rows, bnb, dual, patch_only)
+        hit = tuning.cached(key)
+        if hit is not None:  # steady state: no per-launch walk over the variant table
+            return hit
+        M, N = geom.M, geom.N
+        pseg = pro.seg_rows if pro is not None else 0
+        cands = []
+        for v in range(ops.igemm_nvariants()):
+            bm = ops.igemm_variant_bm(v)
+            if dual:
+                if not ops.igemm_dual_ok(v, geom):
+                    continue
+            elif not ops.igemm_variant_ok(v, geom, pro is not None, bnb, emode):
+                continue  # e.g. LDS-DMA variants: C % 64 == 0, BN-apply prologue only on 1x1
+            if self.want_stats and M % bm:
+                continue
+            if pseg % bm or self.seg_rows % bm:
+                continue
+            if patch_only and not ops.igemm_variant_patch(v):
+                continue
+            cands.append(v)
+        if not cands:
+            raise ValueError(f"no igemm tile variant admissible for M={M} segment rows "
+                             f"{self.seg_rows or pseg}")
+        default = 1 if N <= 64 else 0
+        if default not in cands:
+            default = cands[0]
+
+        def trial(v):
+            # every output of a trial is scratch (tuning.py: trials touch no live tensor), the
+            # block-output prologue's out / mask included; no second statistics stream, and
+            # the BN-backward operand is not stored
+            bm = ops.igemm_variant_bm(v)
+            st = (torch.empty(((M + bm - 1) // bm) * 2 * N, device=self.out.device,
+                              dtype=torch.float32) if self.want_stats else None)
+            self._issue(ops, v, torch.empty_like(self.out), StatsOut(st),
+                        torch.empty_like(pro.out) if dual else None,
+                        torch.empty_like(pro.mask) if dual else None)
+
+        return tuning.pick(key, cands, default, trial)
+
+    def launch(self, ops, v: int, stats: StatsOut = _NO_STATS) -> None:
+        pro = self.pro or _NO_PRO
+        self._issue(ops, v, self.out, stats, pro.out, pro.mask)
+
+
+def run_igemm(ops, A, B, out, geom, bias=None, want_stats=False, pro: Optional[BnApply] = None,
+              epi: Optional[Epilogue] = None):
+    """Launch the implicit GEMM with the autotuned tile variant for this problem; without an
+    admissible variant for the statistics it runs without them.  Returns (stats, nblk) or
+    None."""
+    job = Igemm(A, B, out, geom, bias, want_stats, pro, epi)
     try:
-        v = igemm_choose(ops, A, B, out, geom, bias, want_stats, pro, epi)
+        v = job.choose(ops)
     except ValueError:
         if pro is not None:
             raise ValueError("BN prologue fusion impossible for this shape")
-        want_stats = False
-        v = igemm_choose(ops, A, B, out, geom, bias, False, pro, epi)
-    bm = ops.igemm_variant_bm(v)
-    stats = None
-    if want_stats:
-        stats = torch.empty(((M // bm) * 2 * N,), device=out.device, dtype=torch.float32)
-    igemm_launch(ops, A, B, out, geom, v, bias, stats, pro, epi)
-    return (stats, M // bm) if stats is not None else None
-
-
+        job = job._replace(want_stats=False)
+        v = job.choose(ops)
+    if not job.want_stats:
+        job.launch(ops, v)
+        return None
+    nblk = geom.M // ops.igemm_variant_bm(v)
+    stats = torch.empty((nblk * 2 * geom.N,), device=out.device, dtype=torch.float32)
+    job.launch(ops, v, StatsOut(stats))
+    return stats, nblk
 
 
 # weight gradients issued beside the dgrad / BatchNorm chain (the fused executor's side stream)
@@ -151,44 +349,75 @@ def run_igemm(ops, A, B, out, geom, bias=None, want_stats=False, pro=None, epi=N
 CONCURRENT_MAX_TILE = 256 * 128
 
 
-def run_wgrad(ops, dY, X, out, geom, creal, pro=None, dpro=None, concurrent: bool = False):
-    """Split-M weight gradient (fp32, written to ``out`` = OHWI) with the autotuned variant.
+class WgradX(NamedTuple):
+    """X-operand prologue of the weight gradient: x = relu?(sc[seg]·X + sh[seg]), the BatchNorm
+    (+ ReLU) the forward applied on its input; ``S`` segments of ``seg_rows`` rows."""
+    sc: Optional[torch.Tensor]
+    sh: Optional[torch.Tensor]
+    seg_rows: int
+    relu: bool
+    S: int
 
-    ``dpro = (dY2, coef[3][S][N], seg_rows, S)``: the dY operand is the BatchNorm backward
-    A·dY + B·dY2 + D computed on the fly (splits are aligned to the segments).
+
+class WgradDY(NamedTuple):
+    """dY-operand prologue: dy = A·dY + B·dY2 + D, the BatchNorm backward (``coef``
+    [3][S][N]) computed on the fly; the splits are aligned to the ``S`` segments."""
+    dY2: Optional[torch.Tensor]
+    coef: Optional[torch.Tensor]
+    seg_rows: int
+    S: int
+
+
+_NO_WX = WgradX(None, None, 0, False, 1)
+_NO_WDY = WgradDY(None, None, 0, 1)
+
+
+def run_wgrad(ops, dY, X, out, geom, creal, pro: Optional[WgradX] = None,
+              dpro: Optional[WgradDY] = None, concurrent: bool = False,
+              one_split: bool = False) -> None:
+    """Weight gradient (fp32, written to ``out`` = OHWI) with the autotuned variant: split
+    over M into partials that the op reduces, or with ``one_split`` (few rows: the output tiles
+    alone fill the chip) as ONE split written straight into ``out``, no reduction.
+
     ``concurrent``: the kernel runs beside the critical chain (``CONCURRENT_MAX_TILE``)."""
-    psc, psh, seg_rows, prelu, pS = pro if pro is not None else (None, None, 0, False, 1)
-    dY2, dcoef, dseg, dS = dpro if dpro is not None else (None, None, 0, 1)
-    N = geom[14]
-    K = geom[6] * geom[7] * geom[3]
-    M = geom[0] * geom[4] * geom[5]
-    key = ("wgrad", tuple(geom), creal, psc is not None, dpro is not None, concurrent)
+    xp = WgradX._make(pro) if pro is not None else _NO_WX    # (plain tuples of that layout
+    dp = WgradDY._make(dpro) if dpro is not None else _NO_WDY  # are taken too)
+    if one_split:
+        key = ("wgrad1split", tuple(geom), creal, pro is not None, dpro is not None)
+    else:
+        key = ("wgrad", tuple(geom), creal, pro is not None, dpro is not None, concurrent)
 
     def nsplit(v):
         splits = ops.wgrad_splits(geom, v)
         if dpro is None:
             return splits
-        seg_iters = dseg // 64
-        sps = max(1, splits // dS)
+        seg_iters = dp.seg_rows // 64
+        sps = max(1, splits // dp.S)
         while seg_iters % sps:
             sps -= 1
-        return dS * sps
+        return dp.S * sps
 
-    def launch(v, o, trial=False):
-        splits = nsplit(v)
-        partial = torch.empty((splits * N * K,), device=dY.device, dtype=torch.float32)
-        ops.wgrad(dY, X, partial, o, geom, splits, creal, 0.0, psc, psh, seg_rows, prelu, pS, v,
-                  dY2, dcoef, dseg, dS)
+    def launch(v, o):
+        splits = 1 if one_split else nsplit(v)
+        partial = o if one_split else torch.empty((splits * geom.N * geom.K,), device=dY.device,
+                                                  dtype=torch.float32)
+        ops.wgrad(dY, X, partial, o, geom, splits, creal, 0.0,
+                  pro_sc=xp.sc, pro_sh=xp.sh, pro_seg_rows=xp.seg_rows, pro_relu=xp.relu,
+                  pro_S=xp.S, variant=v, dY2=dp.dY2, dp_coef=dp.coef, dp_seg_rows=dp.seg_rows,
+                  dp_S=dp.S)
 
     v = tuning.cached(key)
     if v is None:
         cands = [v for v in range(ops.wgrad_nvariants())
-                 if ops.wgrad_variant_ok(v, geom, psc is not None, dpro is not None)]
-        if concurrent:
+                 if ops.wgrad_variant_ok(v, geom, pro is not None, dpro is not None)]
+        if one_split:  # the dY prologue of one split: register-staged variants (they take the
+            # per-row view segment)
+            cands = [c for c in cands if dpro is None or not ops.wgrad_variant_glds(c)]
+        elif concurrent:
             cands = [c for c in cands
                      if ops.wgrad_variant_area(c) <= CONCURRENT_MAX_TILE] or cands
-        v = tuning.pick(key, cands, 1 if N <= 64 else 0,
-                        lambda vv: launch(vv, torch.empty_like(out), trial=True))
+        default = 0 if one_split else (1 if geom.N <= 64 else 0)
+        v = tuning.pick(key, cands, default, lambda vv: launch(vv, torch.empty_like(out)))
     launch(v, out)
 
 
@@ -204,15 +433,6 @@ def _nhwc(t: torch.Tensor) -> torch.Tensor:
 def _empty_cl(n, c, h, w, device, dtype=torch.bfloat16):
     return torch.empty((n, c, h, w), device=device, dtype=dtype,
                        memory_format=torch.channels_last)
-
-
-def fwd_geom(N, H, W, C, OH, OW, KH, KW, stride, pad, Co):
-    return [N, H, W, C, OH, OW, KH, KW, stride, stride, 1, 1, -pad, -pad, Co,
-            OH, OW, 1, 1, 0, 0, Co]
-
-
-def _pair(v):
-    return (v, v) if isinstance(v, int) else tuple(v)
 
 
 def shadow_ohwi(weight: torch.Tensor, cpad: int) -> torch.Tensor:
@@ -278,44 +498,17 @@ class ConvHipFn(torch.autograd.Function):
         return dx, dw, None, None, None
 
 
-_WT_CACHE: dict = {}
-
-
 def conv_dgrad(ops, dyn, w_ohwi, N, H, W, Ci, OH, OW, KH, KW, stride, pad, Co):
     """dx [N, Ci, H, W] (channels_last) from dy (NHWC view) and the OHWI bf16 weight."""
-    dev = dyn.device
-    dx = _empty_cl(N, Ci, H, W, dev)
+    dx = _empty_cl(N, Ci, H, W, dyn.device)
     dxn = dx.permute(0, 2, 3, 1)
-    if stride == 1:
-        wt = torch.empty((Ci, KH, KW, Co), device=dev, dtype=torch.bfloat16)
-        ops.weight_transform(w_ohwi, wt, [Co, KH, KW, Ci, KH, KW, KH - 1, -1, KW - 1, -1])
-        g = [N, OH, OW, Co, H, W, KH, KW, 1, 1, 1, 1, -(KH - 1 - pad), -(KW - 1 - pad), Ci,
-             H, W, 1, 1, 0, 0, Ci]
-        run_igemm(ops, dyn, wt, dxn, g)
-        return dx
-    assert stride == 2, "only stride 1/2 convolutions are supported"
-    classes = []
-    for r in (0, 1):
-        for c in (0, 1):
-            kh0 = (r + pad) % 2
-            kw0 = (c + pad) % 2
-            nkh = (KH - kh0 + 1) // 2 if kh0 < KH else 0
-            nkw = (KW - kw0 + 1) // 2 if kw0 < KW else 0
-            ohc = (H - r + 1) // 2
-            owc = (W - c + 1) // 2
-            classes.append((r, c, kh0, kw0, nkh, nkw, ohc, owc))
-    if any(cl[4] == 0 or cl[5] == 0 for cl in classes if cl[6] > 0 and cl[7] > 0):
+    plan = dgrad_plan(N, H, W, Ci, OH, OW, Co, (KH, KW), stride, pad)
+    if plan.zero_fill:
         dx.zero_()
-    for (r, c, kh0, kw0, nkh, nkw, ohc, owc) in classes:
-        if nkh == 0 or nkw == 0 or ohc == 0 or owc == 0:
-            continue
-        wt = torch.empty((Ci, nkh, nkw, Co), device=dev, dtype=torch.bfloat16)
-        ops.weight_transform(w_ohwi, wt, [Co, KH, KW, Ci, nkh, nkw, kh0, 2, kw0, 2])
-        ih0 = (r + pad - kh0) // 2
-        iw0 = (c + pad - kw0) // 2
-        g = [N, OH, OW, Co, ohc, owc, nkh, nkw, 1, 1, -1, -1, ih0, iw0, Ci,
-             H, W, 2, 2, r, c, Ci]
-        run_igemm(ops, dyn, wt, dxn, g)
+    for ln in plan.launches:
+        wt = torch.empty(ln.wt_shape, device=dyn.device, dtype=torch.bfloat16)
+        ops.weight_transform(w_ohwi, wt, ln.wt)
+        run_igemm(ops, dyn, wt, dxn, ln.geom)
     return dx
 
 

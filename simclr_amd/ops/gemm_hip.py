@@ -10,11 +10,7 @@ from typing import Optional
 import torch
 
 from . import _ext
-from .conv_hip import run_igemm, run_wgrad
-
-
-def _geom(M, K, N):
-    return [M, 1, 1, K, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, N, 1, 1, 1, 1, 0, 0, N]
+from .conv_hip import gemm_geom, run_igemm, run_wgrad
 
 
 def _weight_bf16(weight: torch.Tensor) -> torch.Tensor:
@@ -34,7 +30,7 @@ class LinearHipFn(torch.autograd.Function):
         w = _weight_bf16(weight)
         y = torch.empty((M, N), device=x.device, dtype=torch.bfloat16)
         b = bias.detach().float().contiguous() if bias is not None else None
-        res = run_igemm(ops, xc, w, y, _geom(M, K, N), bias=b, want_stats=emit_stats)
+        res = run_igemm(ops, xc, w, y, gemm_geom(M, K, N), bias=b, want_stats=emit_stats)
         if res is not None:
             y._simclr_stats = res
         ctx.save_for_backward(xc, weight, bias)
@@ -54,10 +50,10 @@ class LinearHipFn(torch.autograd.Function):
             wt = torch.empty((K, N), device=dy.device, dtype=torch.bfloat16)
             ops.weight_transform(_weight_bf16(weight), wt, [N, 1, 1, K, 1, 1, 0, 1, 0, 1])
             dx = torch.empty((M, K), device=dy.device, dtype=torch.bfloat16)
-            run_igemm(ops, dyc, wt, dx, _geom(M, N, K))
+            run_igemm(ops, dyc, wt, dx, gemm_geom(M, N, K))
         dw = db = None
         if ctx.needs_input_grad[1]:
-            g = _geom(M, K, N)
+            g = gemm_geom(M, K, N)
             slot = getattr(weight, "_slot", None)
             out = slot.grad if slot is not None else torch.empty(
                 (N, K), device=dy.device, dtype=torch.float32)

@@ -14,34 +14,29 @@ def main():
     spec = importlib.util.spec_from_file_location("bench_main", os.path.join(root, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
-    from simclr_amd.ops import conv_hip
-    import simclr_amd.models.fused as fused
-    orig = conv_hip.igemm_launch
+    from simclr_amd.ops.conv_hip import Igemm
+    orig = Igemm.launch
 
-    def wrapped(ops, A, B, out, geom, v, *a, **kw):
+    def wrapped(job, ops, v, stats=None):
+        args = (stats,) if stats is not None else ()
+        orig(job, ops, v, *args)
         if v != 20:
-            return orig(ops, A, B, out, geom, v, *a, **kw)
-        stats = kw.get("stats")
-        epi = kw.get("epi")
-        mode = epi[0] if epi is not None else 0
-        orig(ops, A, B, out, geom, v, *a, **kw)
-        if mode not in (0, 3) or kw.get("tail") is not None:
+            return
+        mode = job.epi.mode if job.epi is not None else 0
+        if mode not in (0, 3):
             print("skip compare mode", mode, flush=True)
             return
-        out2 = torch.empty_like(out)
-        kw2 = dict(kw)
-        if stats is not None:
-            kw2["stats"] = torch.empty_like(stats)
-        orig(ops, A, B, out2, geom, 15, *a, **kw2)
+        job2 = job._replace(out=torch.empty_like(job.out))
+        stats2 = stats._replace(stats=torch.empty_like(stats.stats)) if stats is not None else None
+        orig(job2, ops, 15, *((stats2,) if stats2 is not None else ()))
         torch.cuda.synchronize()
-        d = (out.float() - out2.float()).abs().max().item()
-        s = out2.float().abs().max().item()
-        ds = ((stats - kw2["stats"]).abs().max().item() if stats is not None else 0.0)
-        print(f"v20 mode {mode} M={geom[0]*geom[4]*geom[5]} out maxdiff {d:.3e} (max {s:.3e})"
-              f" stats maxdiff {ds:.3e} nan={bool(torch.isnan(out).any())}", flush=True)
+        d = (job.out.float() - job2.out.float()).abs().max().item()
+        s = job2.out.float().abs().max().item()
+        ds = ((stats.stats - stats2.stats).abs().max().item() if stats is not None else 0.0)
+        print(f"v20 mode {mode} M={job.geom.M} out maxdiff {d:.3e} (max {s:.3e})"
+              f" stats maxdiff {ds:.3e} nan={bool(torch.isnan(job.out).any())}", flush=True)
 
-    conv_hip.igemm_launch = wrapped
-    fused.igemm_launch = wrapped
+    Igemm.launch = wrapped
     sys.argv = ["bench.py", "--steps", "2", "--warmup", "1", "--no-graph"]
     bench.main()
 
