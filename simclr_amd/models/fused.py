@@ -92,6 +92,22 @@ def _deliver_grad(param: torch.Tensor, compute) -> None:
         param.grad.add_(g)
 
 
+def _out_hw(h: int, k: int, stride: int, pad: int) -> int:
+    """Output extent of a k-tap window over ``h`` positions."""
+    return (h + 2 * pad - k) // stride + 1
+
+
+def _nhwc(t: torch.Tensor, bf16: bool = False) -> torch.Tensor:
+    """Contiguous [N, H, W, C] view of an NCHW tensor (a channels_last copy if it is not one
+    already); ``bf16``: cast first."""
+    if bf16 and t.dtype != torch.bfloat16:
+        t = t.to(torch.bfloat16)
+    tn = t.permute(0, 2, 3, 1)
+    if not tn.is_contiguous():
+        tn = t.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+    return tn
+
+
 @dataclass
 class _ConvSpec:
     conv: torch.nn.Module
@@ -99,6 +115,16 @@ class _ConvSpec:
     stride: int
     k: int
     pad: int
+
+    @classmethod
+    def of(cls, conv, bn) -> "_ConvSpec":
+        """Kernel, stride and padding as the (square) conv module states them."""
+        k, stride, pad = (v[0] if isinstance(v, tuple) else v
+                          for v in (conv.kernel_size, conv.stride, conv.padding))
+        return cls(conv, bn, stride, k, pad)
+
+    def out_hw(self, h: int) -> int:
+        return _out_hw(h, self.k, self.stride, self.pad)
 
 
 @dataclass
@@ -194,15 +220,196 @@ class BnBwdDist(NamedTuple):
 _BWD1X1_BPS = 128
 
 
+def bn_fwd(ops, bn, partial, nblk_seg: int, rows_seg: int, S: int, st, slot: int = 0) -> _BNState:
+    """The BatchNorm state of ``bn`` from a conv epilogue's Σ, Σ² partials: one reduce /
+    finalize launch.  ``slot``: ticket array of the last-arriver reduce (1 on the downsample
+    stream, so a concurrent reduce on the main stream never shares its counters)."""
+    C = bn.num_features
+    dev = partial.device
+    count = float(rows_seg * st.world_size)
+    mi = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
+    ss = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
+    ipc = st.ipc
+    if _SKIP_BNRED in ("fwd", "all"):
+        return _BNState(mi, ss.view(2, S * C), count)
+    if not st.comm or ipc is not None:
+        # one launch: reduce + finalize (last-arriver); at world > 1 the IPC statistics
+        # exchange runs inside it (comm/ipc.py)
+        ops.bn_reduce_fused(partial, nblk_seg, S, C, 1, count=count, eps=bn.eps,
+                            momentum=bn.momentum, rm=bn.running_mean, rv=bn.running_var,
+                            mi=mi, nbt=bn.num_batches_tracked, gamma=bn.weight.detach(),
+                            beta=bn.bias.detach(), ss=ss, ticket_slot=slot,
+                            **(ipc.kwargs(site_key(bn, "fwd"), S, C) if ipc is not None else {}))
+    else:
+        stats = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
+        ops.bn_reduce_fused(partial, nblk_seg, S, C, 0, stats=stats, ticket_slot=slot)
+        _allreduce(stats, st, branch=slot == 1)
+        ops.bn_finalize(stats, S, C, count, bn.eps, bn.momentum, bn.running_mean,
+                        bn.running_var, mi, bn.num_batches_tracked,
+                        gamma=bn.weight.detach(), beta=bn.bias.detach(), ss=ss)
+    return _BNState(mi, ss.view(2, S * C), count)
+
+
+def deliver_bn_grads(bn, run) -> None:
+    """``run(dgamma_out, dbeta_out)`` writes dγ, dβ; route them into the flat store."""
+    gslot = getattr(bn.weight, "_slot", None)
+    bslot = getattr(bn.bias, "_slot", None)
+    if gslot is not None and bslot is not None:
+        run(gslot.grad, bslot.grad)
+        gslot.store.mark_ready(gslot.index)
+        bslot.store.mark_ready(bslot.index)
+        return
+    C = bn.num_features
+    dg = torch.empty((C,), device=bn.weight.device, dtype=torch.float32)
+    db = torch.empty((C,), device=bn.weight.device, dtype=torch.float32)
+    run(dg, db)
+    _deliver_grad(bn.weight, lambda o: o.copy_(dg))
+    _deliver_grad(bn.bias, lambda o: o.copy_(db))
+
+
+def bn_bwd_start(ops, bn, partial, nblk_seg: int, bs: _BNState, S: int, st):
+    """Phase 1 of a BN backward from Σg, Σg·x̂ partials.
+
+    Distributed: reduce to the LOCAL [2][S][C] sums, write dγ, dβ from them (SyncBN
+    semantics: parameter gradients are per-rank and summed by the data-parallel reducer
+    like every other gradient — using the all-reduced sums here would count them W
+    times), then start the all-reduce of the sums asynchronously; the caller schedules
+    independent work (a weight gradient) before ``bn_bwd_finish``.  Single GPU: nothing
+    to wait for (one fused launch in the finish)."""
+    C = bn.num_features
+    if not st.comm or st.ipc is not None:
+        return BnBwdLocal("local", bn, partial, nblk_seg, bs, st.ipc)
+    dev = partial.device
+    sums = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
+    # one launch: the local sums (all-reduced below) and dγ, dβ from them
+    deliver_bn_grads(bn, lambda dg, db: ops.bn_reduce_fused(
+        partial, nblk_seg, S, C, 0, stats=sums, dgamma=dg, dbeta=db))
+    work = dist.all_reduce(sums, group=st.stats_group, async_op=True)
+    return BnBwdDist("dist", bn, sums, work, bs)
+
+
+def bn_bwd_finish(ops, h: Union[BnBwdLocal, BnBwdDist], S: int) -> torch.Tensor:
+    """Phase 2: coef [3][S][C] for the input gradient (from the global sums)."""
+    bn, bs = h.bn, h.bs
+    C = bn.num_features
+    dev = bs.mi.device
+    coef = torch.empty((3 * S * C,), device=dev, dtype=torch.float32)
+    if _SKIP_BNRED in ("bwd", "all"):
+        return coef
+    if isinstance(h, BnBwdLocal):
+        # single launch; with the IPC exchange dγ, dβ come from the local sums and coef
+        # from the global ones (SyncBN semantics, see bn_bwd_start)
+        kw = h.ipc.kwargs(site_key(bn, "bwd"), S, C) if h.ipc is not None else {}
+        deliver_bn_grads(bn, lambda dg, db: ops.bn_reduce_fused(
+            h.partial, h.nblk_seg, S, C, 2, count=bs.count, eps=0.0, momentum=0.0, mi=bs.mi,
+            gamma=bn.weight.detach(), dgamma=dg, dbeta=db, coef=coef, **kw))
+    else:
+        h.work.wait()
+        ops.bn_bwd_finalize(h.sums, bs.mi, bn.weight.detach(), S, C, bs.count, None, None,
+                            coef)
+    return coef
+
+
+class _OutGrad(NamedTuple):
+    """What the backward of a block's output (BN_L + shortcut + ReLU) hands to its convs."""
+    g3: torch.Tensor                    # g·[out > 0]
+    da: torch.Tensor                    # BN_L's input gradient (not written when ``lazy``)
+    lazy: Optional[LazyBN]              # BN_L's backward left to conv L's operand prologues
+    dad: Optional[torch.Tensor]         # the downsample BN's input gradient, materialised, or
+    ds_dual: Optional[tuple]            # (g3, coefd) for the fused pass that never writes it
+
+
 class FusedStages:
     """Executor over ``resnet.layer1..layer4`` (modules stay the parameter / state owners).
 
-    The fusion switches below are instance attributes (tests and A/B tools flip them on a built
-    executor); the class attribute ``BLOCK_OUT_PROLOGUE`` is the default of new executors."""
+    The fusion switches are class-level defaults, so an executor made without the constructor
+    (tests of the launch helpers) reads the same values; tests and A/B tools flip them on an
+    instance.  ``BLOCK_OUT_PROLOGUE`` / ``STEM_FUSED`` are copied at construction."""
 
     BLOCK_OUT_PROLOGUE = True
     # SIMCLR_FUSED_STEM=0: the stem stays on the per-module path (A/B attribution)
     STEM_FUSED = os.environ.get("SIMCLR_FUSED_STEM", "1") != "0"
+
+    # BN backward of a bottleneck's conv3 inside conv3's dgrad/wgrad operand prologues
+    # (only up to 128 input channels: measured net loss or break-even above, r2 log)
+    bnb_prologue = True
+    _bnb_max_cin = 128
+    # BN1's backward in conv1's operand prologues as well: measured +0.85 ms/step (r4 log)
+    lazy_bn1 = False
+    # expansion convs from this many input channels on read a materialised BN2+ReLU input
+    # (_mat_expand)
+    mat_expand_min_cin = 128
+    # a downsample block's output gradient: BN3's backward in conv3's operand prologues and
+    # only the downsample BN's gradient materialised (one-output apply instead of the
+    # two-output bn_bwd_apply2) where conv3's backward is the fused 1x1 kernel (layer1.0):
+    # -0.12 ms/step (3 of 3 A/B rounds); also on the other prologue-eligible conv3s
+    # (layer2.0, register-staged weight gradient) neutral to worse (r4 optimisation log)
+    lazy_bn3_ds = True
+    _lazy_bn3_ds_dual_only = True
+    # a 3x3 stride-1 conv2's output-gradient BatchNorm backward (BN2) in its patch-kernel
+    # dgrad prologue, which also stores it for the weight gradient: one pass instead of a
+    # bn_bwd_apply pass plus the dgrad's re-read (layer1 / layer2; _patch_bnb_ok)
+    patch_bnb = os.environ.get("SIMCLR_PATCH_BNB", "1") != "0"
+    # weight gradients on a second stream (forked after each conv's dY is final, joined at
+    # the end of the backward): they only feed the flat gradient buffer, so they overlap the
+    # dgrad / BatchNorm chain that the next layer's gradient depends on
+    wgrad_stream = os.environ.get("SIMCLR_WGRAD_STREAM", "1") != "0"
+    # the downsample branch of a stage's first block (forward conv + BN, backward dgrad) on
+    # its own stream, concurrent with the main branch until the block output / conv1 dgrad
+    branch_stream = os.environ.get("SIMCLR_BRANCH_STREAM", "1") != "0"
+    # a stride-2 1x1 downsample's dgrad is kept compact ([N, H/2, W/2, C]: it only reaches
+    # the even positions) and added by conv1's dgrad epilogue through the subsampled-residual
+    # mode — instead of zero-filling a full-resolution tensor (0.9 GB/step of fills at
+    # ResNet-50 CIFAR) and re-reading it whole
+    compact_ds = True
+    # a block's output (BN3 + shortcut + ReLU) formed inside the next block's conv1 prologue
+    # instead of a separate pass that conv1 re-reads, at every stage (the prologue kernels
+    # keep their DMA pipelined: 24.06 -> 23.80 ms/step A/B, r2 optimisation log)
+    block_out_min_hw = 1
+    block_out_prologue = BLOCK_OUT_PROLOGUE
+    # a bottleneck's conv3 backward at Ci = 64 / Co = 256 (ResNet-50 layer1) as ONE fused
+    # pass (conv.hip conv1x1_bwd_dual): dgrad + BN2 mask / partials + weight gradient, so the
+    # 0.5-1 GB output gradient is read once instead of once per pass
+    fused_bwd1x1 = True
+    # ... and the wide form at Ci = 128 / Co = 512 (ResNet-50 layer2 conv3; conv.hip
+    # conv1x1_bwd_dual_w: the Ci slices of a row range share each dY tile through L2), which
+    # also takes the forward's materialised BN2+ReLU input (_mat_expand) as its X operand
+    fused_bwd1x1_wide = True
+    # the narrow fused 1x1 backward (Co 256 / Ci 64) as the 8-wave kernel
+    # (conv1x1_bwd_dual_w, 64-row tiles) instead of the 4-wave one: -0.03..-0.08 ms/step,
+    # 3 of 3 rounds (r6 log)
+    dual8 = True
+    # the fused 1x1 backward kernels' weight-gradient slab reduction on the main stream
+    # (serial, ~10 µs at the full chip) instead of the weight-gradient stream
+    dual_reduce_main = False
+    # a stride-1 1x1 downsample of the narrow shape (layer1.0, Co 256 / Ci 64) whose BatchNorm
+    # backward is lazy: its dgrad and weight gradient from one pass over g and its pre-BN
+    # activation (the plain form of conv1x1_bwd_dual) instead of a BN-apply pass writing
+    # its input gradient, a dgrad and a weight gradient each reading it; on the main stream
+    # ("main") or the downsample branch stream ("branch")
+    fused_ds_dual = True
+    ds_dual_stream = "main"
+    # ... and layer2.0's stride-2 downsample (Co 512 / Ci 256, dY materialised): measured
+    # neutral to +0.06 ms (r6 log), so off by default
+    fused_ds_dual_s2 = False
+    # persistent blocks per view segment of the fused 1x1 backward kernels (A/B knobs):
+    # narrow form / layer1.0 downsample, and the wide form (x 2 Ci slices)
+    bwd1x1_bps = _BWD1X1_BPS
+    bwd1x1_bps_wide = 64
+    # the ImageNet stem (7x7 / stride 2 / pad 3 over the 3 image channels) as a 4x4 / stride-1
+    # conv over the 2x2 space-to-depth of the padded image (csrc/eval.hip k_stem_s2d):
+    # K 256 instead of 392 gathered columns, 32-byte instead of 16-byte gathers
+    stem_s2d = True
+
+    # created on first use: the weight-gradient and downsample-branch streams, the batched
+    # dgrad-weight transform of the whole backbone (one launch per backward) and the event of
+    # its prefetch, the space-to-depth image of the current step
+    _side = _branch = _wt_event = _s2d_cache = _wt_sig = _wt_table = None
+    _wt_ready = False
+    # the stem conv + BN where the executor can run it, and the ImageNet stem's max-pool (k,
+    # stride, pad), fused around (stem_forward / backward): BN + ReLU + max-pool in one pass,
+    # the max-pool / ReLU / BN backward in one pass
+    stem = _stem_block = stem_pool = None
 
     def __init__(self, resnet: torch.nn.Module, segments: int = 2):
         from .resnet import BasicBlock, Bottleneck
@@ -212,89 +419,11 @@ class FusedStages:
         # launch accounting (tests): block outputs formed in a conv1 prologue / as their own pass
         self.dual_launches = 0
         self.out_apply_calls = 0
-        # BN backward of a bottleneck's conv3 inside conv3's dgrad/wgrad operand prologues
-        # (only up to 128 input channels: measured net loss or break-even above, r2 log)
-        self.bnb_prologue = True
-        self._bnb_max_cin = 128
-        # BN1's backward in conv1's operand prologues as well: measured +0.85 ms/step (r4 log)
-        self.lazy_bn1 = False
-        # expansion convs from this many input channels on read a materialised BN2+ReLU input
-        # (_mat_expand)
-        self.mat_expand_min_cin = 128
-        # a downsample block's output gradient: BN3's backward in conv3's operand prologues and
-        # only the downsample BN's gradient materialised (one-output apply instead of the
-        # two-output bn_bwd_apply2) where conv3's backward is the fused 1x1 kernel (layer1.0):
-        # -0.12 ms/step (3 of 3 A/B rounds); also on the other prologue-eligible conv3s
-        # (layer2.0, register-staged weight gradient) neutral to worse (r4 optimisation log)
-        self.lazy_bn3_ds = True
-        self._lazy_bn3_ds_dual_only = True
-        # a 3x3 stride-1 conv2's output-gradient BatchNorm backward (BN2) in its patch-kernel
-        # dgrad prologue, which also stores it for the weight gradient: one pass instead of a
-        # bn_bwd_apply pass plus the dgrad's re-read (layer1 / layer2; _patch_bnb_ok)
-        self.patch_bnb = os.environ.get("SIMCLR_PATCH_BNB", "1") != "0"
-        # weight gradients on a second stream (forked after each conv's dY is final, joined at
-        # the end of the backward): they only feed the flat gradient buffer, so they overlap the
-        # dgrad / BatchNorm chain that the next layer's gradient depends on
-        self.wgrad_stream = os.environ.get("SIMCLR_WGRAD_STREAM", "1") != "0"
-        self._side = None
-        # the downsample branch of a stage's first block (forward conv + BN, backward dgrad) on
-        # its own stream, concurrent with the main branch until the block output / conv1 dgrad
-        self.branch_stream = os.environ.get("SIMCLR_BRANCH_STREAM", "1") != "0"
-        # a stride-2 1x1 downsample's dgrad is kept compact ([N, H/2, W/2, C]: it only reaches
-        # the even positions) and added by conv1's dgrad epilogue through the subsampled-residual
-        # mode — instead of zero-filling a full-resolution tensor (0.9 GB/step of fills at
-        # ResNet-50 CIFAR) and re-reading it whole
-        self.compact_ds = True
-        self._branch = None
-        # a block's output (BN3 + shortcut + ReLU) formed inside the next block's conv1 prologue
-        # instead of a separate pass that conv1 re-reads, at every stage (the prologue kernels
-        # keep their DMA pipelined: 24.06 -> 23.80 ms/step A/B, r2 optimisation log)
-        self.block_out_min_hw = 1
-        self.block_out_prologue = type(self).BLOCK_OUT_PROLOGUE
-        # a bottleneck's conv3 backward at Ci = 64 / Co = 256 (ResNet-50 layer1) as ONE fused
-        # pass (conv.hip conv1x1_bwd_dual): dgrad + BN2 mask / partials + weight gradient, so the
-        # 0.5-1 GB output gradient is read once instead of once per pass
-        self.fused_bwd1x1 = True
-        # ... and the wide form at Ci = 128 / Co = 512 (ResNet-50 layer2 conv3; conv.hip
-        # conv1x1_bwd_dual_w: the Ci slices of a row range share each dY tile through L2), which
-        # also takes the forward's materialised BN2+ReLU input (_mat_expand) as its X operand
-        self.fused_bwd1x1_wide = True
-        # a stride-1 1x1 downsample of that shape (layer1.0, Co 256 / Ci 64) whose BatchNorm
-        # backward is lazy: its dgrad and weight gradient from one pass over g and its pre-BN
-        # activation (the plain form of conv1x1_bwd_dual) instead of a BN-apply pass writing
-        # its input gradient, a dgrad and a weight gradient each reading it; on the main stream
-        # ("main") or the downsample branch stream ("branch")
-        # the narrow fused 1x1 backward (Co 256 / Ci 64) as the 8-wave kernel
-        # (conv1x1_bwd_dual_w, 64-row tiles) instead of the 4-wave one: -0.03..-0.08 ms/step,
-        # 3 of 3 rounds (r6 log)
-        self.dual8 = True
-        # the fused 1x1 backward kernels' weight-gradient slab reduction on the main stream
-        # (serial, ~10 µs at the full chip) instead of the weight-gradient stream
-        self.dual_reduce_main = False
-        self.fused_ds_dual = True
-        # persistent blocks per view segment of the fused 1x1 backward kernels (A/B knobs):
-        # narrow form / layer1.0 downsample, and the wide form (x 2 Ci slices)
-        self.bwd1x1_bps = _BWD1X1_BPS
-        self.bwd1x1_bps_wide = 64
-        # the ImageNet stem (7x7 / stride 2 / pad 3 over the 3 image channels) as a 4x4 / stride-1
-        # conv over the 2x2 space-to-depth of the padded image (csrc/eval.hip k_stem_s2d):
-        # K 256 instead of 392 gathered columns, 32-byte instead of 16-byte gathers
-        self.stem_s2d = True
-        # ... and layer2.0's stride-2 downsample (Co 512 / Ci 256, dY materialised): measured
-        # neutral to +0.06 ms (r6 log), so off by default
-        self.fused_ds_dual_s2 = False
-        self.ds_dual_stream = "main"
         self._side_keep: List[torch.Tensor] = []
-        # dgrad weight transforms of the whole backbone: one batched launch per backward
-        self._wt_sig = None
         self._wt_cache = {}
-        self._wt_table = None
-        self._wt_ready = False
-        # the stem (conv1 + bn1 + ReLU, when no max-pool follows) inside the executor: its BatchNorm
-        # backward partials come from layer1.0's conv1 dgrad epilogue (mode 4, like every block
-        # boundary) and its weight gradient applies the BN backward in the dY prologue — no
-        # separate reduce pass over the 1024 x 32 x 32 x 64 stem activation, no materialised
-        # input gradient (stem_forward / backward)
+        self._dual_cache = {}
+        self._patch_bnb_cache = {}
+        self.block_out_prologue = type(self).BLOCK_OUT_PROLOGUE
         # A/B of the fusion switches above without code edits (tools/envab.sh):
         # SIMCLR_FUSED_ATTRS="attr=value,..." (ints / true / false / strings), applied at
         # construction
@@ -310,38 +439,22 @@ class FusedStages:
                 except ValueError:
                     setattr(self, k, v)
         self.stem_fused = type(self).STEM_FUSED
-        self.stem = None
-        self._stem_block = None
-        # the ImageNet stem's max-pool (k, stride, pad), fused around (stem_forward / backward):
-        # BN + ReLU + max-pool in one pass, the max-pool / ReLU / BN backward in one pass
-        self.stem_pool = None
         from .resnet import _Identity
         from ..ops.pooling import MaxPool2d
         mp = getattr(resnet, "maxpool", None)
         if isinstance(mp, (_Identity, MaxPool2d)):
-            c1 = resnet.conv1
-            k = c1.kernel_size[0] if isinstance(c1.kernel_size, tuple) else c1.kernel_size
-            st_ = c1.stride[0] if isinstance(c1.stride, tuple) else c1.stride
-            pd = c1.padding[0] if isinstance(c1.padding, tuple) else c1.padding
-            self.stem = _ConvSpec(c1, resnet.bn1, st_, k, pd)
+            self.stem = _ConvSpec.of(resnet.conv1, resnet.bn1)
             self._stem_block = _BlockSpec([self.stem], None, "stem")
             if isinstance(mp, MaxPool2d):
                 self.stem_pool = (int(mp.kernel_size), int(mp.stride), int(mp.padding))
         self.blocks: List[_BlockSpec] = []
         for li, layer in enumerate((resnet.layer1, resnet.layer2, resnet.layer3, resnet.layer4)):
             for bi, blk in enumerate(layer):
-                if isinstance(blk, Bottleneck):
-                    convs = [_ConvSpec(blk.conv1, blk.bn1, 1, 1, 0),
-                             _ConvSpec(blk.conv2, blk.bn2, blk.stride, 3, 1),
-                             _ConvSpec(blk.conv3, blk.bn3, 1, 1, 0)]
-                elif isinstance(blk, BasicBlock):
-                    convs = [_ConvSpec(blk.conv1, blk.bn1, blk.stride, 3, 1),
-                             _ConvSpec(blk.conv2, blk.bn2, 1, 3, 1)]
-                else:
+                if not isinstance(blk, (Bottleneck, BasicBlock)):
                     raise TypeError(f"unsupported block {type(blk).__name__}")
-                down = None
-                if blk.downsample is not None:
-                    down = _ConvSpec(blk.downsample[0], blk.downsample[1], blk.stride, 1, 0)
+                convs = [_ConvSpec.of(getattr(blk, f"conv{i}"), getattr(blk, f"bn{i}"))
+                         for i in range(1, 4 if isinstance(blk, Bottleneck) else 3)]
+                down = _ConvSpec.of(*blk.downsample) if blk.downsample is not None else None
                 self.blocks.append(_BlockSpec(convs, down, f"layer{li + 1}.{bi}"))
 
     # ------------------------------------------------------------------ feasibility
@@ -356,23 +469,19 @@ class FusedStages:
         """The image batch can enter at the stem: a stem conv without max-pool, an input that
         needs no gradient, and stem-output rows per view that tile (256-row BatchNorm-backward
         prologue splits of the stem weight gradient)."""
-        if not (getattr(self, "stem_fused", False) and self.stem is not None):
+        if not (self.stem_fused and self.stem is not None):
             return False
         if (img.requires_grad or img.dtype != torch.bfloat16 or not img.is_cuda
                 or img.dim() != 4 or img.shape[1] % 8 or img.shape[1] < self.stem.conv.in_channels):
             return False
         Nb, _, H, W = img.shape
-        cs = self.stem
-        OH = (H + 2 * cs.pad - cs.k) // cs.stride + 1
-        OW = (W + 2 * cs.pad - cs.k) // cs.stride + 1
+        OH, OW = self.stem.out_hw(H), self.stem.out_hw(W)
         if self.stem_pool is not None:
             # the stem weight gradient reads a materialised BN input gradient (no 256-row
             # BN-backward prologue splits); the blocks see the pooled map
-            K, Sd, P = self.stem_pool
             if Nb % self.S or ((Nb // self.S) * OH * OW) % 64 or self.stem.conv.out_channels % 8:
                 return False
-            PH, PW = (OH + 2 * P - K) // Sd + 1, (OW + 2 * P - K) // Sd + 1
-            return self._shape_ok(Nb, PH, PW)
+            return self._shape_ok(Nb, _out_hw(OH, *self.stem_pool), _out_hw(OW, *self.stem_pool))
         if Nb % self.S or ((Nb // self.S) * OH * OW) % 256:
             return False
         return self._shape_ok(Nb, OH, OW)
@@ -384,7 +493,7 @@ class FusedStages:
         for b in self.blocks:
             hin = H
             for i, cs in enumerate(b.convs):
-                oh = (hin + 2 * cs.pad - cs.k) // cs.stride + 1
+                oh = cs.out_hw(hin)
                 if (n * oh * oh) % 64:
                     return False
                 if cs.stride == 2:  # BN-epilogue dgrad: per parity-class segments
@@ -406,7 +515,7 @@ class FusedStages:
 
     def _s2d_ok(self, cs: _ConvSpec, xn: torch.Tensor) -> bool:
         """The stem conv runs in its space-to-depth form (``stem_s2d``)."""
-        if not (getattr(self, "stem_s2d", False) and cs is self.stem and xn.is_cuda):
+        if not (self.stem_s2d and cs is self.stem and xn.is_cuda):
             return False
         Nb, H, W, C = xn.shape
         return (cs.k == 7 and cs.stride == 2 and cs.pad == 3 and cs.conv.in_channels <= 4
@@ -415,7 +524,7 @@ class FusedStages:
     def _s2d_input(self, ops, xn: torch.Tensor) -> torch.Tensor:
         """[Nb, (H+6)/2, (W+6)/2, 16]: the padded image, 2x2 space-to-depth (kept for the
         weight gradient of the same step)."""
-        c = getattr(self, "_s2d_cache", None)
+        c = self._s2d_cache
         if c is not None and c[0] is xn:
             return c[1]
         Nb, H, W, _ = xn.shape
@@ -453,8 +562,7 @@ class FusedStages:
         (``_bn_fwd``)."""
         Nb, H, W, C = xn.shape
         Co = cs.conv.out_channels
-        OH = (H + 2 * cs.pad - cs.k) // cs.stride + 1
-        OW = (W + 2 * cs.pad - cs.k) // cs.stride + 1
+        OH, OW = cs.out_hw(H), cs.out_hw(W)
         a = _empty_nhwc(Nb, OH, OW, Co, xn.device)
         if dual is None and pro_ss is None and self._s2d_ok(cs, xn):
             xn = self._s2d_input(ops, xn)
@@ -481,14 +589,14 @@ class FusedStages:
     def _dual_ok(self, ops, xn, cs: _ConvSpec, S: int) -> bool:
         """Can ``cs`` (a block's conv1) form its input — the previous block's output — in its
         prologue (1x1 / stride 1 / unpadded, an LDS-DMA tile that fits the doubled staging)?"""
-        if not (getattr(self, "block_out_prologue", False) and xn.is_cuda and cs.k == 1
+        if not (self.block_out_prologue and xn.is_cuda and cs.k == 1
                 and cs.stride == 1 and cs.pad == 0):
             return False
         Nb, H, W, C = xn.shape
-        if H < getattr(self, "block_out_min_hw", 1):
+        if H < self.block_out_min_hw:
             return False
         key = (Nb, H, W, C, cs.conv.out_channels, S)
-        cache = self.__dict__.setdefault("_dual_cache", {})
+        cache = self._memo("_dual_cache")
         if key not in cache:  # host-side admissibility, once per shape
             g = fwd_geom(Nb, H, W, C, H, W, 1, 1, 1, 0, cs.conv.out_channels)
             M = Nb * H * W
@@ -498,93 +606,53 @@ class FusedStages:
 
     def _bn_fwd(self, ops, bn, partial, nblk_seg: int, rows_seg: int, S: int, st,
                 slot: int = 0) -> _BNState:
-        """``slot``: ticket array of the last-arriver reduce (1 on the downsample stream, so a
-        concurrent reduce on the main stream never shares its counters)."""
-        C = bn.num_features
-        dev = partial.device
-        count = float(rows_seg * st.world_size)
-        mi = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
-        ss = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
-        ipc = st.ipc
-        if _SKIP_BNRED in ("fwd", "all"):
-            return _BNState(mi, ss.view(2, S * C), count)
-        if not st.comm or ipc is not None:
-            # one launch: reduce + finalize (last-arriver); at world > 1 the IPC statistics
-            # exchange runs inside it (comm/ipc.py)
-            ops.bn_reduce_fused(partial, nblk_seg, S, C, 1, count=count, eps=bn.eps,
-                                momentum=bn.momentum, rm=bn.running_mean, rv=bn.running_var,
-                                mi=mi, nbt=bn.num_batches_tracked, gamma=bn.weight.detach(),
-                                beta=bn.bias.detach(), ss=ss, ticket_slot=slot,
-                                **(ipc.kwargs(site_key(bn, "fwd"), S, C) if ipc is not None else {}))
-        else:
-            stats = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
-            ops.bn_reduce_fused(partial, nblk_seg, S, C, 0, stats=stats, ticket_slot=slot)
-            _allreduce(stats, st, branch=slot == 1)
-            ops.bn_finalize(stats, S, C, count, bn.eps, bn.momentum, bn.running_mean,
-                            bn.running_var, mi, bn.num_batches_tracked,
-                            gamma=bn.weight.detach(), beta=bn.bias.detach(), ss=ss)
-        return _BNState(mi, ss.view(2, S * C), count)
+        return bn_fwd(ops, bn, partial, nblk_seg, rows_seg, S, st, slot)
 
-    def _deliver_bn_grads(self, bn, run) -> None:
-        """``run(dgamma_out, dbeta_out)`` writes dγ, dβ; route them into the flat store."""
-        gslot = getattr(bn.weight, "_slot", None)
-        bslot = getattr(bn.bias, "_slot", None)
-        if gslot is not None and bslot is not None:
-            run(gslot.grad, bslot.grad)
-            gslot.store.mark_ready(gslot.index)
-            bslot.store.mark_ready(bslot.index)
-            return
-        C = bn.num_features
-        dg = torch.empty((C,), device=bn.weight.device, dtype=torch.float32)
-        db = torch.empty((C,), device=bn.weight.device, dtype=torch.float32)
-        run(dg, db)
-        _deliver_grad(bn.weight, lambda o: o.copy_(dg))
-        _deliver_grad(bn.bias, lambda o: o.copy_(db))
-
+    # the BatchNorm backward of the module-level functions, as methods: the executor calls
+    # these (tests wrap them on the class to see every BatchNorm the executor runs)
     def _bn_bwd_start(self, ops, bn, partial, nblk_seg: int, bs: _BNState, S: int, st):
-        """Phase 1 of a BN backward from Σg, Σg·x̂ partials.
-
-        Distributed: reduce to the LOCAL [2][S][C] sums, write dγ, dβ from them (SyncBN
-        semantics: parameter gradients are per-rank and summed by the data-parallel reducer
-        like every other gradient — using the all-reduced sums here would count them W
-        times), then start the all-reduce of the sums asynchronously; the caller schedules
-        independent work (a weight gradient) before ``_bn_bwd_finish``.  Single GPU: nothing
-        to wait for (one fused launch in the finish)."""
-        C = bn.num_features
-        if not st.comm or st.ipc is not None:
-            return BnBwdLocal("local", bn, partial, nblk_seg, bs, st.ipc)
-        dev = partial.device
-        sums = torch.empty((2 * S * C,), device=dev, dtype=torch.float32)
-        # one launch: the local sums (all-reduced below) and dγ, dβ from them
-        self._deliver_bn_grads(bn, lambda dg, db: ops.bn_reduce_fused(
-            partial, nblk_seg, S, C, 0, stats=sums, dgamma=dg, dbeta=db))
-        work = dist.all_reduce(sums, group=st.stats_group, async_op=True)
-        return BnBwdDist("dist", bn, sums, work, bs)
+        return bn_bwd_start(ops, bn, partial, nblk_seg, bs, S, st)
 
     def _bn_bwd_finish(self, ops, h: Union[BnBwdLocal, BnBwdDist], S: int) -> torch.Tensor:
-        """Phase 2: coef [3][S][C] for the input gradient (from the global sums)."""
-        bn, bs = h.bn, h.bs
-        C = bn.num_features
-        dev = bs.mi.device
-        coef = torch.empty((3 * S * C,), device=dev, dtype=torch.float32)
-        if _SKIP_BNRED in ("bwd", "all"):
-            return coef
-        if isinstance(h, BnBwdLocal):
-            # single launch; with the IPC exchange dγ, dβ come from the local sums and coef
-            # from the global ones (SyncBN semantics, see _bn_bwd_start)
-            kw = h.ipc.kwargs(site_key(bn, "bwd"), S, C) if h.ipc is not None else {}
-            self._deliver_bn_grads(bn, lambda dg, db: ops.bn_reduce_fused(
-                h.partial, h.nblk_seg, S, C, 2, count=bs.count, eps=0.0, momentum=0.0, mi=bs.mi,
-                gamma=bn.weight.detach(), dgamma=dg, dbeta=db, coef=coef, **kw))
-        else:
-            h.work.wait()
-            ops.bn_bwd_finalize(h.sums, bs.mi, bn.weight.detach(), S, C, bs.count, None, None,
-                                coef)
-        return coef
+        return bn_bwd_finish(ops, h, S)
 
     def _bn_bwd(self, ops, bn, partial, nblk_seg: int, bs: _BNState, S: int, st) -> torch.Tensor:
         return self._bn_bwd_finish(ops, self._bn_bwd_start(ops, bn, partial, nblk_seg, bs, S, st),
                                    S)
+
+    def _memo(self, name: str) -> dict:
+        """A per-instance cache of host-side admissibility answers; an executor made without
+        the constructor creates it on first use."""
+        if name not in vars(self):
+            setattr(self, name, {})
+        return vars(self)[name]
+
+    def _side_stream(self, dev) -> "torch.cuda.Stream":
+        """The weight-gradient stream of ``dev``, created on first use."""
+        if self._side is None or self._side.device != dev:
+            self._side = torch.cuda.Stream(device=dev)
+        return self._side
+
+    def _issue_wgrad(self, cs: _ConvSpec, keep, compute, main: bool = False) -> None:
+        """Deliver the weight gradient of ``cs`` (``compute(out)`` writes it) on the
+        weight-gradient stream, forked here — or in line.  ``keep``: what ``compute`` reads,
+        referenced until the join (the caching allocator must not hand that memory to a
+        main-stream allocation while the side stream still reads it)."""
+        if _SKIP_WGRAD:  # attribution experiment only: the step without weight gradients
+            compute = lambda out: None  # noqa: E731
+        side = self._side if self.wgrad_stream and not main else None
+        if side is None:
+            _deliver_grad(cs.conv.weight, compute)
+            return
+        self._side_keep.extend(keep)
+        side.wait_stream(torch.cuda.current_stream(keep[0].device))
+        with torch.cuda.stream(side):
+            _deliver_grad(cs.conv.weight, compute)
+
+    def _reduce_slabs(self, ops, cs: _ConvSpec, wpart: torch.Tensor, nslab: int) -> None:
+        """The weight gradient of ``cs`` from the per-block slabs of a fused 1x1 backward."""
+        self._issue_wgrad(cs, (wpart,), lambda out: ops.wgrad_reduce_slabs(wpart, nslab, out),
+                          main=self.dual_reduce_main)
 
     def _wgrad(self, ops, dyn, xn, cs: _ConvSpec, pro_ss: Optional[torch.Tensor], S: int,
                bnb: Optional[LazyBN] = None, main: bool = False):
@@ -600,39 +668,22 @@ class FusedStages:
         else:
             g = fwd_geom(Nb, H, W, C, OH, OW, cs.k, cs.k, cs.stride, cs.pad, Co)
         M = Nb * OH * OW
-        pro = None
-        if pro_ss is not None:
-            pro = WgradX(pro_ss[0], pro_ss[1], M // S, True, S)
+        pro = WgradX(pro_ss[0], pro_ss[1], M // S, True, S) if pro_ss is not None else None
         dpro = WgradDY(*bnb, M // S, S) if bnb is not None else None
 
-        side = getattr(self, "_side", None) if getattr(self, "wgrad_stream", False) else None
-        concurrent = side is not None and not main
+        concurrent = bool(self.wgrad_stream) and self._side is not None and not main
 
-        def run():
-            if _SKIP_WGRAD:  # attribution experiment only: the step without weight gradients
-                _deliver_grad(cs.conv.weight, lambda out: None)
-                return
+        def compute(out):
             if s2d:  # the 4x4 form's gradient, folded back onto the 7x7 kernel
-                def s2d_grad(out):
-                    gs = torch.empty((Co, 4, 4, 16), device=dyn.device, dtype=torch.float32)
-                    run_wgrad(ops, dyn, xn, gs, g, 16, pro=pro, dpro=dpro, concurrent=concurrent)
-                    self._s2d_unfold_grad(gs, out)
-                _deliver_grad(cs.conv.weight, s2d_grad)
-                return
-            # creal: the stem's 3 image channels are gathered as 8 (zero-padded)
-            _deliver_grad(cs.conv.weight,
-                          lambda out: run_wgrad(ops, dyn, xn, out, g, cs.conv.in_channels,
-                                                pro=pro, dpro=dpro, concurrent=concurrent))
+                gs = torch.empty((Co, 4, 4, 16), device=dyn.device, dtype=torch.float32)
+                run_wgrad(ops, dyn, xn, gs, g, 16, pro=pro, dpro=dpro, concurrent=concurrent)
+                self._s2d_unfold_grad(gs, out)
+            else:  # creal: the stem's 3 image channels are gathered as 8 (zero-padded)
+                run_wgrad(ops, dyn, xn, out, g, cs.conv.in_channels, pro=pro, dpro=dpro,
+                          concurrent=concurrent)
 
-        if side is None or main:
-            run()
-            return
-        # operands stay referenced until the join (the caching allocator must not hand their
-        # memory to a main-stream allocation while the side stream still reads them)
-        self._side_keep.extend(t for t in (dyn, xn, pro_ss, *(bnb or ())) if t is not None)
-        side.wait_stream(torch.cuda.current_stream(dyn.device))
-        with torch.cuda.stream(side):
-            run()
+        self._issue_wgrad(cs, [t for t in (dyn, xn, pro_ss, *(bnb or ())) if t is not None],
+                          compute, main)
 
     @staticmethod
     def _bwd1x1_bps(rows_seg: int, cap: int = _BWD1X1_BPS) -> int:
@@ -646,13 +697,13 @@ class FusedStages:
     def _bwd1x1_ok(self, cs: _ConvSpec, dyn: torch.Tensor, xin: torch.Tensor, pro_ss, a_prev,
                    S: int) -> bool:
         M = dyn.numel() // dyn.shape[-1]
-        if not (getattr(self, "fused_bwd1x1", False) and cs.k == 1 and cs.stride == 1
+        if not (self.fused_bwd1x1 and cs.k == 1 and cs.stride == 1
                 and M % S == 0 and (M // S) % 64 == 0):
             return False
         co, ci = cs.conv.out_channels, cs.conv.in_channels
         if (co, ci) == (256, 64):
             return xin is a_prev and pro_ss is not None and M * 256 * 2 < (1 << 31)
-        if (co, ci) == (512, 128) and getattr(self, "fused_bwd1x1_wide", False):
+        if (co, ci) == (512, 128) and self.fused_bwd1x1_wide:
             # X: a2 with the BN2 prologue, or the forward's materialised relu(bn2(a2))
             return ((xin is a_prev and pro_ss is not None)
                     or (pro_ss is None and xin.shape == a_prev.shape)) and M * 512 * 2 < (1 << 31)
@@ -672,9 +723,7 @@ class FusedStages:
         # segment fill the chip's 256 CUs once at S = 2
         bps = self._bwd1x1_bps(M // S, self.bwd1x1_bps_wide if wide else self.bwd1x1_bps)
         xraw = xin if (wide and xin is not None and xin is not a_prev) else None
-        w = shadow_ohwi(cs.conv.weight, Ci)
-        wt = self._dgrad_weight(ops, cs, w,
-                                dgrad_plan(Nb, H, W, Ci, H, W, Co, 1, 1, 0).launches[0])
+        wt = self._dgrad_weight1x1(ops, cs, a_prev.shape, H, W)
         dev = dyn.device
         gm = _empty_nhwc(Nb, H, W, Ci, dev)
         stats = torch.empty((S * bps * 2 * Ci,), device=dev, dtype=torch.float32)
@@ -686,25 +735,8 @@ class FusedStages:
         else:
             ops.conv1x1_bwd_dual(dyn, a3, coef, a_prev, bs_prev.ss.view(-1),
                                  bs_prev.mi.view(-1), wt, gm, stats, wpart, S, bps,
-                                 dual8=bool(getattr(self, "dual8", False)))
-
-        def run():
-            if _SKIP_WGRAD:
-                _deliver_grad(cs.conv.weight, lambda out: None)
-                return
-            _deliver_grad(cs.conv.weight,
-                          lambda out: ops.wgrad_reduce_slabs(wpart, S * bps, out))
-
-        side = getattr(self, "_side", None) if getattr(self, "wgrad_stream", False) else None
-        if getattr(self, "dual_reduce_main", False):
-            side = None
-        if side is None:
-            run()
-        else:
-            self._side_keep.append(wpart)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                run()
+                                 dual8=bool(self.dual8))
+        self._reduce_slabs(ops, cs, wpart, S * bps)
         return gm, stats, bps
 
     def _ds_dual_ok(self, b: _BlockSpec, tp: _BlockTape, S: int) -> bool:
@@ -712,8 +744,8 @@ class FusedStages:
         narrow dual shape (Co 256 / Ci 64, lazy BN backward), or stride 2 at Co 512 / Ci 256
         (layer2.0; dY materialised: ``_ds_dual_s2``)."""
         cs = b.down
-        if not (getattr(self, "fused_ds_dual", False) and getattr(self, "fused_bwd1x1", False)
-                and tp.x.is_cuda and cs.k == 1 and cs.pad == 0 and b.convs[0].stride == 1):
+        if not (self.fused_ds_dual and self.fused_bwd1x1 and tp.x.is_cuda and cs.k == 1
+                and cs.pad == 0 and b.convs[0].stride == 1):
             return False
         Nb, H, W, Ci = tp.x.shape
         shape = (cs.conv.out_channels, cs.conv.in_channels)
@@ -721,8 +753,8 @@ class FusedStages:
             M = Nb * H * W
             return (shape == (256, 64) and Ci == 64 and M % S == 0 and (M // S) % 64 == 0
                     and M * 256 * 2 < (1 << 31))
-        if cs.stride == 2 and getattr(self, "fused_ds_dual_s2", False):
-            Mo = Nb * ((H + 1) // 2) * ((W + 1) // 2)
+        if cs.stride == 2 and self.fused_ds_dual_s2:
+            Mo = Nb * cs.out_hw(H) * cs.out_hw(W)
             return (shape == (512, 256) and Ci == 256 and Nb % S == 0 and (Mo // S) % 64 == 0
                     and Mo * 512 * 2 < (1 << 31) and tp.x.numel() * 2 < (1 << 31))
         return False
@@ -738,47 +770,24 @@ class FusedStages:
         Co = cs.conv.out_channels
         dev = g3.device
         _ext.TAG = f"{b.name} ds dgrad+wgrad"
-        if cs.stride == 2:
+        s2 = cs.stride == 2
+        OH, OW = cs.out_hw(H), cs.out_hw(W)
+        if s2:
             # layer2.0: dY materialised (the lazy form of the wide kernel spills), then ONE pass
             # for the compact input gradient and the weight gradient (strided X)
-            OH, OW = (H + 1) // 2, (W + 1) // 2
             dad = torch.empty_like(tp.ad)
             ops.bn_bwd_apply(g3, None, tp.ad, coefd, S, False, dad, None)
-            bps = self._bwd1x1_bps(Nb * OH * OW // S, 32)
-            w = shadow_ohwi(cs.conv.weight, Ci)
-            wt = self._dgrad_weight(ops, cs, w, dgrad_plan(Nb, H, W, Ci, OH, OW, Co, 1, 2, 0,
-                                                           compact=True).launches[0])
-            resid = _empty_nhwc(Nb, OH, OW, Ci, dev)
-            wpart = torch.empty((S * bps * Co * Ci,), device=dev, dtype=torch.float32)
+        bps = self._bwd1x1_bps(Nb * OH * OW // S, 32 if s2 else self.bwd1x1_bps)
+        wt = self._dgrad_weight1x1(ops, cs, tp.x.shape, OH, OW, compact=s2)
+        resid = _empty_nhwc(Nb, OH, OW, Ci, dev)
+        wpart = torch.empty((S * bps * Co * Ci,), device=dev, dtype=torch.float32)
+        if s2:
             ops.conv1x1_bwd_dual_s2(dad, None, None, tp.x, wt, resid, wpart, S, bps)
         else:
-            M = Nb * H * W
-            bps = self._bwd1x1_bps(M // S, self.bwd1x1_bps)
-            w = shadow_ohwi(cs.conv.weight, Ci)
-            wt = self._dgrad_weight(ops, cs, w,
-                                    dgrad_plan(Nb, H, W, Ci, H, W, Co, 1, 1, 0).launches[0])
-            resid = _empty_nhwc(Nb, H, W, Ci, dev)
-            wpart = torch.empty((S * bps * Co * Ci,), device=dev, dtype=torch.float32)
             nostats = torch.empty((1,), device=dev, dtype=torch.float32)
             ops.conv1x1_bwd_dual(g3, tp.ad, coefd, tp.x, None, None, wt, resid, nostats, wpart,
-                                 S, bps, dual8=bool(getattr(self, "dual8", False)))
-
-        def run():
-            if _SKIP_WGRAD:
-                _deliver_grad(cs.conv.weight, lambda out: None)
-                return
-            _deliver_grad(cs.conv.weight, lambda out: ops.wgrad_reduce_slabs(wpart, S * bps, out))
-
-        side = getattr(self, "_side", None) if getattr(self, "wgrad_stream", False) else None
-        if getattr(self, "dual_reduce_main", False):
-            side = None
-        if side is None:
-            run()
-        else:
-            self._side_keep.append(wpart)
-            side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side):
-                run()
+                                 S, bps, dual8=bool(self.dual8))
+        self._reduce_slabs(ops, cs, wpart, S * bps)
         return resid
 
     def _bnb_ok(self, cs: _ConvSpec, a: torch.Tensor, S: int) -> bool:
@@ -790,7 +799,7 @@ class FusedStages:
         (measured on layer3/layer4 of ResNet-50: net loss or break-even)."""
         M = a.numel() // a.shape[-1]
         return (self.bnb_prologue and cs.k == 1 and cs.stride == 1 and M % S == 0
-                and (M // S) % 256 == 0 and cs.conv.in_channels <= getattr(self, "_bnb_max_cin", 128))
+                and (M // S) % 256 == 0 and cs.conv.in_channels <= self._bnb_max_cin)
 
     def _mat_expand(self, cs: _ConvSpec) -> bool:
         """A bottleneck's expansion 1x1 conv (conv3, Co = 4 Ci) takes its input BN2+ReLU as a
@@ -805,9 +814,9 @@ class FusedStages:
 
     def _lazy_bn3_ds_ok(self, b: _BlockSpec, tp: _BlockTape, aL: torch.Tensor, S: int) -> bool:
         L = len(b.convs) - 1
-        if not (getattr(self, "lazy_bn3_ds", False) and L > 0 and self._bnb_ok(b.convs[L], aL, S)):
+        if not (self.lazy_bn3_ds and L > 0 and self._bnb_ok(b.convs[L], aL, S)):
             return False
-        if not getattr(self, "_lazy_bn3_ds_dual_only", True):
+        if not self._lazy_bn3_ds_dual_only:
             return True
         xin, pro_ss = tp.ins[L]
         return self._bwd1x1_ok(b.convs[L], aL, xin, pro_ss, tp.acts[L - 1], S)
@@ -824,7 +833,7 @@ class FusedStages:
             return False
         Ci = cs.conv.in_channels
         key = (Nb, H, W, C, Ci)
-        cache = self.__dict__.setdefault("_patch_bnb_cache", {})
+        cache = self._memo("_patch_bnb_cache")
         if key not in cache:
             g = dgrad_plan(Nb, H, W, Ci, H, W, C, 3, 1, 1).launches[0].geom
             cache[key] = any(ops.igemm_variant_patch(v) and ops.igemm_variant_ok(v, g, True, True)
@@ -836,7 +845,7 @@ class FusedStages:
         of a materialising pass (a bottleneck's 1x1 stride-1 conv1)."""
         cs0 = b.convs[0]
         M = a1.numel() // a1.shape[-1]
-        return (getattr(self, "lazy_bn1", False) and cs0.k == 1 and cs0.stride == 1
+        return (self.lazy_bn1 and cs0.k == 1 and cs0.stride == 1
                 and M % S == 0 and (M // S) % 256 == 0)
 
     def _dgrad(self, ops, dyn, cs: _ConvSpec, in_shape, S: int, accumulate: bool = False,
@@ -928,7 +937,7 @@ class FusedStages:
         of its plan (``conv_hip.dgrad_plan``).  The parameters depend on the conv alone, not on
         the image: any extent with all four parity classes (2 x 2 on) gives them."""
         conv = cs.conv
-        OH = (2 + 2 * cs.pad - cs.k) // cs.stride + 1
+        OH = cs.out_hw(2)
         plan = dgrad_plan(1, 2, 2, conv.in_channels, OH, OH, conv.out_channels, cs.k, cs.stride,
                           cs.pad)
         return [(ln.key, ln.wt) for ln in plan.launches]
@@ -973,28 +982,33 @@ class FusedStages:
         self._wt_event = None
         if not (self.wgrad_stream and xn.is_cuda):
             return
-        dev = xn.device
-        if self._side is None or self._side.device != dev:
-            self._side = torch.cuda.Stream(device=dev)
-        self._side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(self._side):
+        side = self._side_stream(xn.device)
+        side.wait_stream(torch.cuda.current_stream(xn.device))
+        with torch.cuda.stream(side):
             self.prepare_backward(ops)
         if self._wt_ready:
             ev = torch.cuda.Event()
-            ev.record(self._side)
+            ev.record(side)
             self._wt_event = ev
 
     def _dgrad_weight(self, ops, cs: _ConvSpec, w, ln: DgradLaunch):
         """The transformed weight of one dgrad launch: from the batched transform
         (prepare_backward) when it ran, else transformed here."""
         shape = ln.wt_shape
-        if getattr(self, "_wt_ready", False):
+        if self._wt_ready:
             wt = self._wt_cache.get((id(cs.conv), ln.key))
             if wt is not None and wt.shape[0] == shape[0]:
                 return wt
         wt = torch.empty(shape, device=w.device, dtype=torch.bfloat16)
         ops.weight_transform(w, wt, ln.wt)
         return wt
+
+    def _dgrad_weight1x1(self, ops, cs: _ConvSpec, in_shape, OH: int, OW: int,
+                         compact: bool = False):
+        """The transformed weight of a 1x1 conv's dgrad (its first / only launch)."""
+        Nb, H, W, Ci = in_shape
+        plan = dgrad_plan(Nb, H, W, Ci, OH, OW, cs.conv.out_channels, 1, cs.stride, 0, compact)
+        return self._dgrad_weight(ops, cs, shadow_ohwi(cs.conv.weight, Ci), plan.launches[0])
 
     # ------------------------------------------------------------------ forward / backward
     def forward(self, xn: torch.Tensor) -> Tuple[torch.Tensor, List[_BlockTape]]:
@@ -1088,8 +1102,7 @@ class FusedStages:
             # maxpool(relu(bn(a))) in one pass; the full-resolution BN output is never written
             K, Sd, P = self.stem_pool
             Nb, OH, OW, C = a.shape
-            PH, PW = (OH + 2 * P - K) // Sd + 1, (OW + 2 * P - K) // Sd + 1
-            x0 = _empty_nhwc(Nb, PH, PW, C, a.device)
+            x0 = _empty_nhwc(Nb, _out_hw(OH, K, Sd, P), _out_hw(OW, K, Sd, P), C, a.device)
             arg = torch.empty(x0.shape, device=a.device, dtype=torch.uint8)
             asel = torch.empty_like(x0)
             _ext.TAG = "stem bn+relu+maxpool"
@@ -1109,7 +1122,7 @@ class FusedStages:
         ops.bn_apply_ss(pend.aL, pend.ss, pend.res, pend.rss, pend.out, S, True, pend.mask)
 
     def _branch_stream(self, t: torch.Tensor):
-        if not (getattr(self, "branch_stream", False) and t.is_cuda):
+        if not (self.branch_stream and t.is_cuda):
             return None
         if self._branch is None or self._branch.device != t.device:
             self._branch = torch.cuda.Stream(device=t.device)
@@ -1125,27 +1138,26 @@ class FusedStages:
         ops = _ext.ops()
         st = pstate.get()
         S = self.S
-        ev = getattr(self, "_wt_event", None)
-        if ev is not None and self._wt_ready:
-            torch.cuda.current_stream(gout.device).wait_event(ev)  # transposed during the forward
+        if self._wt_event is not None and self._wt_ready:
+            # transposed during the forward
+            torch.cuda.current_stream(gout.device).wait_event(self._wt_event)
         else:
             self.prepare_backward(ops)
         self._wt_event = None
         main = None
         if self.wgrad_stream and gout.is_cuda:
             main = torch.cuda.current_stream(gout.device)
-            if self._side is None or self._side.device != gout.device:
-                self._side = torch.cuda.Stream(device=gout.device)
+            side = self._side_stream(gout.device)
             store = self._flat_store()
             if store is not None:
-                store.producer_streams = [main, self._side]
+                store.producer_streams = [main, side]
         g, pre = gout, None
         pooled = stem_tape is not None and stem_tape.pool is not None
         # a pooled stem is not a block-boundary producer (the max-pool sits between its BN and
         # layer1.0): layer1.0 returns the raw gradient of the pooled map
         stem_prev = (self._stem_block, stem_tape) if (stem_tape is not None and not pooled) \
             else None
-        hook = getattr(self.resnet, "stage_grads_ready", None) if main is not None else None
+        hook = self.resnet.stage_grads_ready if main is not None else None
         for idx in range(len(self.blocks) - 1, -1, -1):
             prev = (self.blocks[idx - 1], tapes[idx - 1]) if idx > 0 else stem_prev
             g, pre = self._block_backward(ops, st, S, self.blocks[idx], tapes[idx], g, pre, prev)
@@ -1175,8 +1187,6 @@ class FusedStages:
             ops.maxpool_bwd_bn(g, arg, x0, a0, coef, S, da, K, Sd, P)
             _ext.TAG = "stem wgrad"
             self._wgrad(ops, da, stem_tape.x, self.stem, None, S, main=True)
-            _ext.TAG = ""
-            g = None
         elif stem_tape is not None:
             # g = dL/d(stem output)·[y > 0] with the stem BatchNorm's partials from layer1.0's
             # conv1 dgrad epilogue: finish its backward, weight gradient with the BN backward in
@@ -1188,8 +1198,9 @@ class FusedStages:
             # still works through layer1.0's (the tail of the step runs both side by side)
             self._wgrad(ops, g, stem_tape.x, self.stem, None, S,
                         bnb=LazyBN(stem_tape.acts[0], coef), main=True)
+        if stem_tape is not None:
             _ext.TAG = ""
-            g = None
+            g = None  # the image needs no gradient
         if main is not None:
             if store is not None and getattr(store, "defer_side_join", False):
                 # joined in store.finish(), after the stem's backward
@@ -1218,6 +1229,26 @@ class FusedStages:
 
         Every BN all-reduce (distributed) is started before an independent weight-gradient
         kernel and finished after it, so its latency hides behind the wgrad."""
+        o = self._out_bn_bwd(ops, st, S, b, tp, g, pre)
+        # (bottleneck blocks: conv1 is 1x1 stride 1, so its dgrad epilogue covers every input
+        # position; a BasicBlock's conv1 carries the stride itself)
+        compact = (b.down is not None and self.compact_ds and b.down.stride == 2 and b.down.k == 1
+                   and b.down.pad == 0 and b.convs[0].stride == 1)
+        resid, join = self._ds_dgrad_start(ops, S, b, tp, o, compact)
+        da, lazy0 = self._chain_bwd(ops, st, S, b, tp, o, prev)
+        dx, h = self._conv1_dgrad(ops, st, S, b, tp, o, da, lazy0, resid, join, compact, prev)
+        _ext.TAG = f"{b.name} conv1 wgrad"
+        self._wgrad(ops, da, tp.x, b.convs[0], None, S, bnb=lazy0)
+        if o.dad is not None:
+            _ext.TAG = f"{b.name} ds wgrad"
+            self._wgrad(ops, o.dad, tp.x, b.down, None, S)
+        _ext.TAG = ""
+        return dx, h
+
+    def _out_bn_bwd(self, ops, st, S, b: _BlockSpec, tp: _BlockTape, g, pre) -> _OutGrad:
+        """Backward of the block output: BN_L from the raw gradient (reduce, apply with the
+        ReLU mask of ``out``) or finished from its started handle (``pre``), then the downsample
+        BN's — both from one pass, or one of them left to its consumer (``_OutGrad``)."""
         out = tp.out
         L = len(b.convs) - 1
         _ext.TAG = f"{b.name} bn{L + 1} bwd"
@@ -1272,27 +1303,35 @@ class FusedStages:
                     ops.bn_bwd_apply2(g3, aL, coefL, da, tp.ad, coefd, dad, S)
                 else:
                     ops.bn_bwd_apply(g3, None, tp.ad, coefd, S, False, dad, None)
-        resid_f = None
-        # (bottleneck blocks: conv1 is 1x1 stride 1, so its dgrad epilogue covers every input
-        # position; a BasicBlock's conv1 carries the stride itself)
-        compact = (b.down is not None and self.compact_ds and b.down.stride == 2 and b.down.k == 1
-                   and b.down.pad == 0 and b.convs[0].stride == 1)
-        br = self._branch_stream(tp.ad) if b.down is not None else None
-        if ds_dual is not None:
-            if br is not None and getattr(self, "ds_dual_stream", "main") == "branch":
+        return _OutGrad(g3, da, lazy, dad, ds_dual)
+
+    def _ds_dgrad_start(self, ops, S, b: _BlockSpec, tp: _BlockTape, o: _OutGrad, compact: bool):
+        """The downsample's input gradient where it can run beside the conv chain: the fused
+        pass (``_ds_dual``) or the dgrad on the branch stream → (it, the stream to join or
+        None); (None, None) leaves the dgrad to ``_conv1_dgrad``."""
+        if b.down is None:
+            return None, None
+        br = self._branch_stream(tp.ad)
+        if o.ds_dual is not None:
+            if br is not None and self.ds_dual_stream == "branch":
                 br.wait_stream(torch.cuda.current_stream(tp.ad.device))
                 with torch.cuda.stream(br):
-                    resid_f = self._ds_dual(ops, b, tp, ds_dual, S)
-            else:
-                resid = self._ds_dual(ops, b, tp, ds_dual, S)
-        elif br is not None:
-            # the downsample dgrad only meets the conv chain at conv1's dgrad epilogue
-            br.wait_stream(torch.cuda.current_stream(dad.device))
-            with torch.cuda.stream(br):
-                _ext.TAG = f"{b.name} ds dgrad"
-                resid_f, _, _ = self._dgrad(ops, dad, b.down, tp.x.shape, S, compact=compact)
-        # conv chain, last to first: dgrad (+ BN-bwd partials) → start BN all-reduce → wgrad →
-        # finish BN → apply
+                    return self._ds_dual(ops, b, tp, o.ds_dual, S), br
+            return self._ds_dual(ops, b, tp, o.ds_dual, S), None
+        if br is None:
+            return None, None
+        # the downsample dgrad only meets the conv chain at conv1's dgrad epilogue
+        br.wait_stream(torch.cuda.current_stream(o.dad.device))
+        with torch.cuda.stream(br):
+            _ext.TAG = f"{b.name} ds dgrad"
+            return self._dgrad(ops, o.dad, b.down, tp.x.shape, S, compact=compact)[0], br
+
+    def _chain_bwd(self, ops, st, S, b: _BlockSpec, tp: _BlockTape, o: _OutGrad, prev):
+        """Convs L..2, last to first: dgrad (+ BN-bwd partials) → start BN all-reduce → wgrad →
+        finish BN → apply.  Returns (da, lazy0): conv1's output gradient, or with ``lazy0``
+        the masked gradient whose BN1 backward is left to conv1's operand prologues."""
+        L = len(b.convs) - 1
+        g3, da, lazy = o.g3, o.da, o.lazy
         lazy0 = None
         pend = None  # (g, LazyBN): the BN backward feeding conv i, left to its patch dgrad
         for i in range(L, 0, -1):
@@ -1310,19 +1349,19 @@ class FusedStages:
                 gm, part, nb = self._dgrad(ops, gsrc, cs, a_prev.shape, S,
                                            bn_epi=MaskEpi("mask", a_prev, bs_prev),
                                            bnb=lazy_b, bnb_out=dy_m)
-                h = self._bn_bwd_start(ops, b.convs[i - 1].bn, part, nb, bs_prev, S, st)
-                _ext.TAG = f"{b.name} conv{i + 1} wgrad"
-                self._wgrad(ops, dy_m, xin, cs, pro_ss, S)
+                wdy, wbnb = dy_m, None
             elif self._bwd1x1_ok(cs, dyn, xin, pro_ss, a_prev, S):
                 _ext.TAG = f"{b.name} conv{i + 1} dgrad+wgrad"
                 gm, part, nb = self._bwd1x1_fused(ops, dyn, bnb, cs, a_prev, bs_prev, S, xin)
-                h = self._bn_bwd_start(ops, b.convs[i - 1].bn, part, nb, bs_prev, S, st)
+                wdy = None  # the weight gradient came from the same launch
             else:
                 gm, part, nb = self._dgrad(ops, dyn, cs, a_prev.shape, S,
                                            bn_epi=MaskEpi("mask", a_prev, bs_prev), bnb=bnb)
-                h = self._bn_bwd_start(ops, b.convs[i - 1].bn, part, nb, bs_prev, S, st)
+                wdy, wbnb = dyn, bnb
+            h = self._bn_bwd_start(ops, b.convs[i - 1].bn, part, nb, bs_prev, S, st)
+            if wdy is not None:
                 _ext.TAG = f"{b.name} conv{i + 1} wgrad"
-                self._wgrad(ops, dyn, xin, cs, pro_ss, S, bnb=bnb)
+                self._wgrad(ops, wdy, xin, cs, pro_ss, S, bnb=wbnb)
             _ext.TAG = f"{b.name} bn{i} bwd"
             coef = self._bn_bwd_finish(ops, h, S)
             if i == 1 and prev is not None and self._lazy_bn1_ok(b, a_prev, S):
@@ -1335,43 +1374,39 @@ class FusedStages:
             da_next = torch.empty_like(a_prev)
             ops.bn_bwd_apply(gm, None, a_prev, coef, S, False, da_next, None)
             da = da_next
+        return da, lazy0
+
+    def _conv1_dgrad(self, ops, st, S, b: _BlockSpec, tp: _BlockTape, o: _OutGrad, da, lazy0,
+                     resid, join, compact: bool, prev):
+        """The block's input gradient: conv1's dgrad plus the residual — the identity path's g3
+        or the downsample's input gradient (joined from ``join``, or its dgrad issued here).
+        With a producer inside the executor (``prev``) the epilogue applies its ReLU mask and
+        emits the partials of its block-output BatchNorm(s), whose backward is started here →
+        (dx, (h3, hd)); otherwise (raw dx, None)."""
         cs0 = b.convs[0]
-        if b.down is not None:
-            if resid_f is not None:
-                torch.cuda.current_stream(tp.ad.device).wait_stream(br)  # join
-                resid = resid_f
-            elif ds_dual is None:
-                _ext.TAG = f"{b.name} ds dgrad"
-                resid, _, _ = self._dgrad(ops, dad, b.down, tp.x.shape, S, compact=compact)
-        else:
-            resid = g3
+        if b.down is None:
+            resid = o.g3
+        elif join is not None:
+            torch.cuda.current_stream(tp.ad.device).wait_stream(join)
+        elif resid is None:
+            _ext.TAG = f"{b.name} ds dgrad"
+            resid, _, _ = self._dgrad(ops, o.dad, b.down, tp.x.shape, S, compact=compact)
         _ext.TAG = f"{b.name} conv1 dgrad"
         if prev is None:
             dx, _, _ = self._dgrad(ops, da, cs0, tp.x.shape, S, accumulate=True, dx=resid,
                                    sub_resid=compact)
-            h = None
-        else:
-            pb, ptp = prev
-            pds = pb.down is not None
-            dx, part, nb = self._dgrad(ops, da, cs0, tp.x.shape, S, bnb=lazy0,
-                                       dx=resid if b.down is not None and not compact else None,
-                                       sub_resid=compact,
-                                       bn_epi=ResEpi("res", resid, ptp.mask, ptp.acts[-1],
-                                                     ptp.bns[-1].mi, ptp.ad if pds else None,
-                                                     ptp.bnd.mi if pds else None))
-            if pds:
-                p3, pd = part
-                h = (self._bn_bwd_start(ops, pb.convs[-1].bn, p3, nb, ptp.bns[-1], S, st),
-                     self._bn_bwd_start(ops, pb.down.bn, pd, nb, ptp.bnd, S, st))
-            else:
-                h = (self._bn_bwd_start(ops, pb.convs[-1].bn, part, nb, ptp.bns[-1], S, st), None)
-        _ext.TAG = f"{b.name} conv1 wgrad"
-        self._wgrad(ops, da, tp.x, cs0, None, S, bnb=lazy0)
-        if b.down is not None and ds_dual is None:
-            _ext.TAG = f"{b.name} ds wgrad"
-            self._wgrad(ops, dad, tp.x, b.down, None, S)
-        _ext.TAG = ""
-        return dx, h
+            return dx, None
+        pb, ptp = prev
+        pds = pb.down is not None
+        dx, part, nb = self._dgrad(ops, da, cs0, tp.x.shape, S, bnb=lazy0,
+                                   dx=resid if b.down is not None and not compact else None,
+                                   sub_resid=compact,
+                                   bn_epi=ResEpi("res", resid, ptp.mask, ptp.acts[-1],
+                                                 ptp.bns[-1].mi, ptp.ad if pds else None,
+                                                 ptp.bnd.mi if pds else None))
+        p3, pd = part if pds else (part, None)
+        return dx, (self._bn_bwd_start(ops, pb.convs[-1].bn, p3, nb, ptp.bns[-1], S, st),
+                    self._bn_bwd_start(ops, pb.down.bn, pd, nb, ptp.bnd, S, st) if pds else None)
 
 
 class FusedStemStagesFn(torch.autograd.Function):
@@ -1381,23 +1416,13 @@ class FusedStemStagesFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, img, anchor, ex: FusedStages):
-        xn = img.permute(0, 2, 3, 1)
-        if not xn.is_contiguous():
-            xn = img.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
-        out, tapes, stem_tape = ex.stem_forward(xn)
+        out, ctx.tapes, ctx.stem_tape = ex.stem_forward(_nhwc(img))
         ctx.ex = ex
-        ctx.tapes = tapes
-        ctx.stem_tape = stem_tape
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gout):
-        if gout.dtype != torch.bfloat16:
-            gout = gout.to(torch.bfloat16)
-        gn = gout.permute(0, 2, 3, 1)
-        if not gn.is_contiguous():
-            gn = gout.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
-        ctx.ex.backward(gn, ctx.tapes, ctx.stem_tape)
+        ctx.ex.backward(_nhwc(gout, bf16=True), ctx.tapes, ctx.stem_tape)
         ctx.tapes = None
         ctx.stem_tape = None
         return None, None, None
@@ -1409,21 +1434,12 @@ class FusedStagesFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, anchor, ex: FusedStages):
-        xn = x.permute(0, 2, 3, 1)
-        if not xn.is_contiguous():
-            xn = x.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
-        out, tapes = ex.forward(xn)
+        out, ctx.tapes = ex.forward(_nhwc(x))
         ctx.ex = ex
-        ctx.tapes = tapes
         return out.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, gout):
-        if gout.dtype != torch.bfloat16:
-            gout = gout.to(torch.bfloat16)
-        gn = gout.permute(0, 2, 3, 1)
-        if not gn.is_contiguous():
-            gn = gout.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
-        dx = ctx.ex.backward(gn, ctx.tapes)
+        dx = ctx.ex.backward(_nhwc(gout, bf16=True), ctx.tapes)
         ctx.tapes = None
         return dx.permute(0, 3, 1, 2), None, None

@@ -38,6 +38,7 @@ from ..ops import _ext
 from ..ops.conv_hip import (BnApply, BnBackward, Epilogue, Igemm, StatsOut, WgradDY, WgradX,
                             gemm_geom, run_wgrad)
 from ..parallel import state as pstate
+from .fused import bn_bwd_finish, bn_bwd_start, bn_fwd
 
 
 def _w16(weight: torch.Tensor) -> torch.Tensor:
@@ -45,11 +46,6 @@ def _w16(weight: torch.Tensor) -> torch.Tensor:
     if slot is not None and slot.shadow is not None:
         return slot.shadow
     return weight.detach().to(torch.bfloat16).contiguous()
-
-
-def _bnops():
-    from .fused import FusedStages
-    return FusedStages.__new__(FusedStages)  # the stateless BatchNorm helpers of the executor
 
 
 def _wgrad_direct(ops, dY, X, out, geom, creal, pro=None, dpro=None):
@@ -171,7 +167,7 @@ class MLPHeadFn(torch.autograd.Function):
         bm = ops.igemm_variant_bm(v)
         part = torch.empty(((M // bm) * 2 * H,), device=dev, dtype=torch.float32)
         gemm1.launch(ops, v, StatsOut(part))
-        bs = _bnops()._bn_fwd(ops, bn, part, seg // bm, seg, S, st)
+        bs = bn_fwd(ops, bn, part, seg // bm, seg, S, st)
         # GEMM 2 on relu(bn(y1)) formed in the operand prologue
         z = torch.empty((M, D), device=dev, dtype=torch.bfloat16)
         bias2 = b2.detach().float().contiguous() if b2 is not None else None
@@ -214,7 +210,6 @@ class MLPHeadFn(torch.autograd.Function):
         dzc = dz.contiguous()
         if dzc.dtype != torch.bfloat16:
             dzc = dzc.to(torch.bfloat16)
-        bnx = _bnops()
         # dgrad 2: g = (dz·W2)·[bn(y1) > 0] with the BN-backward partials Σg, Σg·x̂
         gm = torch.empty((M, H), device=dev, dtype=torch.bfloat16)
         dgrad2 = Igemm(dzc, wt2, gm, gemm_geom(M, D, H), want_stats=True,
@@ -223,7 +218,7 @@ class MLPHeadFn(torch.autograd.Function):
         nb = seg // ops.igemm_variant_bm(v)
         part = torch.empty((S * nb * 2 * H,), device=dev, dtype=torch.float32)
         dgrad2.launch(ops, v, StatsOut(part, seg_blocks=nb))
-        h = bnx._bn_bwd_start(ops, bn, part, nb, bs, S, st)
+        h = bn_bwd_start(ops, bn, part, nb, bs, S, st)
         # dW2 = dzᵀ · relu(bn(y1)) (X prologue), independent of the BN backward
         pro = WgradX(bs.ss[0], bs.ss[1], seg, True, S)
         gw2 = _deliver(lin2.weight, lambda o: _wgrad_direct(ops, dzc, y1, o.view(D, 1, 1, H),
@@ -231,7 +226,7 @@ class MLPHeadFn(torch.autograd.Function):
         gb2 = None
         if ctx.has_b2:
             gb2 = _deliver(lin2.bias, lambda o: ops.colsum(dzc, o, 0.0))
-        coef = bnx._bn_bwd_finish(ops, h, S)
+        coef = bn_bwd_finish(ops, h, S)
         # dgrad 1 with the BN backward da = A·g + B·y1 + D in the A-operand prologue
         dx = None
         if ctx.needs_input_grad[0]:

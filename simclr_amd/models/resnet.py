@@ -159,6 +159,9 @@ class ResNet(nn.Module):
     # the fused stage executor (models/fused.py) runs layer1..layer4 in training on the HIP
     # path; ``use_fused_stages = False`` (or SIMCLR_FUSED=0) keeps the per-module path
     use_fused_stages = os.environ.get("SIMCLR_FUSED", "1") != "0"
+    # called by the executor's backward with a stage number (2..4) once every gradient of that
+    # stage is queued (the trainer hooks the stage's optimizer update here)
+    stage_grads_ready = None
 
     def _fused_executor(self, x: torch.Tensor, segments: int, check: bool = True):
         if not (self.training and self.use_fused_stages and torch.is_grad_enabled()
