@@ -86,6 +86,12 @@ struct IgemmArgs {
   int seg_rows, stats_seg_blocks, stats_base;
 };
 
+// Raw buffer resource over [p, p + bytes): offsets at or past `bytes` load zeros (the gathers'
+// padding and tail handling rests on that).  0x00020000 = DATA_FORMAT 32 bit, no swizzle.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const void* p, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc((void*)p, (short)0, (int)bytes, 0x00020000);
+}
+
 __device__ __forceinline__ u32x4 affine_relu8(u32x4 v, const float* sc, const float* sh, bool ok,
                                               bool relu) {
   u32x4 w;
@@ -430,10 +436,8 @@ __global__ __launch_bounds__(256, (BM * BN > 128 * 128) ? 1 : 2) void igemm_nt(I
   const int mb = lbid / p.nNb, nb = lbid % p.nNb;
   const int m0 = mb * BM, n0 = nb * BN;
 
-  const __amdgpu_buffer_rsrc_t ra_src =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb_src =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.b_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra_src = buf_rsrc(p.A, p.a_bytes);
+  const __amdgpu_buffer_rsrc_t rb_src = buf_rsrc(p.B, p.b_bytes);
 
   const int cch = tid & 7;
   const int rbase = tid >> 3;
@@ -468,8 +472,7 @@ __global__ __launch_bounds__(256, (BM * BN > 128 * 128) ? 1 : 2) void igemm_nt(I
   constexpr bool pro = PRO == 1;
   constexpr bool bnb = PRO == 2;
   const int pseg = (pro || bnb) ? m0 / p.pro_seg_rows : 0;  // block-uniform (host guarantees)
-  const __amdgpu_buffer_rsrc_t ra2_src = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(bnb ? p.A2 : p.A), (short)0, (int)p.a_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra2_src = buf_rsrc(bnb ? p.A2 : p.A, p.a_bytes);
   const uint32_t OOB_A = p.a_bytes, OOB_B = p.b_bytes;
 
   auto gload = [&](int kt) {
@@ -666,12 +669,9 @@ __global__ __launch_bounds__(64 * WM * WN, NST == 1 ? 2 : 1) void igemm_glds(Ige
   const int mb = lbid / p.nNb, nb = lbid % p.nNb;
   const int m0 = mb * BM, n0 = nb * BN;
 
-  const __amdgpu_buffer_rsrc_t ra =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.b_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(PRO >= 2 ? p.A2 : p.A), (short)0, (int)p.a_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra = buf_rsrc(p.A, p.a_bytes);
+  const __amdgpu_buffer_rsrc_t rb = buf_rsrc(p.B, p.b_bytes);
+  const __amdgpu_buffer_rsrc_t rr = buf_rsrc(PRO >= 2 ? p.A2 : p.A, p.a_bytes);
 
   // lane → (row within its 8-row piece, physical chunk); the logical chunk it fetches is
   // pch ^ (row & 7) = pch ^ lrow (every piece starts at a multiple of 8 rows)
@@ -978,10 +978,8 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void igemm_patch(IgemmArgs p) {
   const int img = m0 / OHW;
   const int row0 = (m0 - img * OHW) / OW;
 
-  const __amdgpu_buffer_rsrc_t ra =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.A, (short)0, (int)p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rb =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.B, (short)0, (int)p.b_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t ra = buf_rsrc(p.A, p.a_bytes);
+  const __amdgpu_buffer_rsrc_t rb = buf_rsrc(p.B, p.b_bytes);
 
   const int CPP = C / 8;
   // PRO: chunk c = tid + i·NT of the landed patch sits in pixel q = tid/CPP + i·(NT/CPP) at
@@ -1025,8 +1023,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void igemm_patch(IgemmArgs p) {
   // thread transforms, loaded to registers under the patch DMA (host: <= kPatchBnbChunks each)
   u32x4 a2v[kPatchBnbChunks];
   if (PRO == 2) {
-    const __amdgpu_buffer_rsrc_t r2 =
-        __builtin_amdgcn_make_buffer_rsrc((void*)p.A2, (short)0, (int)p.a_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t r2 = buf_rsrc(p.A2, p.a_bytes);
     const int QS = NT / CPP, q0 = tid / CPP;
     const int lch = (tid % CPP) ^ (q0 & 7);  // the same logical chunk for every i (QS % 8 == 0)
 #pragma unroll
@@ -1396,6 +1393,157 @@ __device__ __forceinline__ void wgrad_store(
                                          k0 + (wid % WN) * (BKK / WN));
 }
 
+template <class T, int FM, int FN>
+__device__ __forceinline__ void zero_acc(T (&acc)[FM][FN]) {
+#pragma unroll
+  for (int i = 0; i < FM; ++i)
+#pragma unroll
+    for (int j = 0; j < FN; ++j) acc[i][j] = T{};
+}
+
+// A block's share of the weight gradient: the (co0, k0) corner of its BCO x BKK tile and rows
+// [mbeg, mend) of its split, walked in nit steps of SR rows.  The host splits M in 64-row units;
+// a trailing split may be empty (mend <= mbeg): it runs no step and stores a zero slab.
+struct WgBlock {
+  int split, co0, k0, mbeg, mend, nit;
+};
+template <int BCO, int BKK, int SR = 64>
+__device__ __forceinline__ WgBlock wg_block(const WgradArgs& p) {
+  const int lbid = xcd_remap(blockIdx.x, gridDim.x);
+  const int tiles = p.nCo * p.nKk;
+  WgBlock b;
+  b.split = lbid / tiles;
+  const int tile = lbid % tiles;
+  b.co0 = (tile / p.nKk) * BCO;
+  b.k0 = (tile % p.nKk) * BKK;
+  b.mbeg = b.split * p.iters_per_split * 64;
+  const int mend_raw = b.mbeg + p.iters_per_split * 64;
+  b.mend = mend_raw < p.M ? mend_raw : p.M;
+  b.nit = b.mend > b.mbeg ? (b.mend - b.mbeg + SR - 1) / SR : 0;
+  return b;
+}
+
+// Incremental im2col addressing of NJ operand rows per thread: every row advances by exactly SR
+// output pixels per step, so (n, oh, ow) are carried forward with compares instead of two integer
+// divisions per chunk per step (those divisions were ~40 % of the loop's VALU work).
+template <int NJ, int SR>
+struct Im2colCursor {
+  int n[NJ], oh[NJ], ow[NJ];
+  int dn, doh, dow;  // SR rows as (images, output rows, output columns)
+  __device__ __forceinline__ void init(const WgradArgs& p) {
+    const int OHW = p.OH * p.OW;
+    dn = SR / OHW;
+    const int dr = SR - dn * OHW;
+    doh = dr / p.OW;
+    dow = dr - doh * p.OW;
+  }
+  __device__ __forceinline__ void seek(const WgradArgs& p, int j, int m) {
+    const int OHW = p.OH * p.OW;
+    n[j] = m / OHW;
+    const int rem = m - n[j] * OHW;
+    oh[j] = rem / p.OW;
+    ow[j] = rem - oh[j] * p.OW;
+  }
+  // Byte offset of row j's 16-byte chunk at channel ci of the tap at (ihb, iwb).  ok: in, row and
+  // column lie inside the problem; out, and the tap inside the image.  Where it does not hold the
+  // offset is p.x_bytes, out of the buffer's range: the load returns zeros.
+  // 24-bit multiplies (full-rate v_mul_u32_u24): every factor is < 2^24 and the byte offset
+  // < 2^31 (host-checked), so the low 32 bits are exact
+  __device__ __forceinline__ uint32_t x_off(const WgradArgs& p, int j, int ihb, int iwb, int ci,
+                                            bool& ok) const {
+    const int ih = (int)__umul24((unsigned)oh[j], (unsigned)p.ish) + ihb;
+    const int iw = (int)__umul24((unsigned)ow[j], (unsigned)p.isw) + iwb;
+    ok = ok && (unsigned)ih < (unsigned)p.IH && (unsigned)iw < (unsigned)p.IW;
+    const uint32_t pix =
+        __umul24(__umul24((unsigned)n[j], (unsigned)p.IH) + (unsigned)ih, (unsigned)p.IW) +
+        (unsigned)iw;
+    return ok ? __umul24(pix, (unsigned)(p.C * 2)) + (uint32_t)(ci * 2) : p.x_bytes;
+  }
+  __device__ __forceinline__ void advance(const WgradArgs& p, int j) {
+    int w = ow[j] + dow, h = oh[j] + doh, i = n[j] + dn;
+    if (w >= p.OW) { w -= p.OW; ++h; }
+    if (h >= p.OH) { h -= p.OH; ++i; }
+    ow[j] = w; oh[j] = h; n[j] = i;
+  }
+};
+
+// dY operand of the LDS-DMA weight gradients (NW waves, steps of SR rows): lane → (row in piece,
+// physical chunk) → the logical column chunk wg_swz maps onto that lane-linear LDS slot.
+template <int BCO, int NW, int SR, int MF>
+struct WgDyLane {
+  static constexpr int CPD = BCO / 8, RPD = 64 / CPD, DI = SR / (RPD * NW);
+  static_assert(DI >= 1 && DI * RPD * NW == SR, "wgrad dY lane mapping");
+  int row[DI];
+  uint32_t off[DI], dstep;
+  bool cok[DI];
+  __device__ __forceinline__ void init(const WgradArgs& p, const WgBlock& blk) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < DI; ++j) {
+      const int r = (j * NW + wid) * RPD + lane / CPD;
+      const int col = blk.co0 + wg_swz<BCO, MF>(r, (lane % CPD) * 8);
+      row[j] = r;
+      cok[j] = col < p.N;
+      off[j] = (uint32_t)(((size_t)(blk.mbeg + r) * p.N + col) * 2);
+    }
+    dstep = (uint32_t)(SR * p.N * 2);
+  }
+  // DMA of step `it` into stage `buf` of Ds ([stages][SR][BCO]); steps are issued in order
+  __device__ __forceinline__ void issue(const WgradArgs& p, __amdgpu_buffer_rsrc_t rd,
+                                        const uint16_t* Ds, int it, int buf, const WgBlock& blk) {
+    const int wid = threadIdx.x >> 6;
+    const int mb = blk.mbeg + it * SR;
+#pragma unroll
+    for (int j = 0; j < DI; ++j) {
+      const bool ok = mb + row[j] < blk.mend && cok[j];
+      dma16_opaque(rd, Ds + buf * SR * BCO + (j * NW + wid) * RPD * BCO, ok ? off[j] : p.dy_bytes);
+      off[j] += dstep;
+    }
+  }
+};
+
+// im2col(X) operand of the same kernels: fixed (tap, channel) per lane and piece (the block's k
+// window is fixed), output pixel carried incrementally.
+template <int BKK, int NW, int SR, int MF>
+struct WgXLane {
+  static constexpr int CPX = BKK / 8, RPX = 64 / CPX, XI = SR / (RPX * NW);
+  static_assert(XI >= 1 && XI * RPX * NW == SR, "wgrad X lane mapping");
+  int row[XI], ci[XI], ihb[XI], iwb[XI];
+  bool kok[XI];
+  Im2colCursor<XI, SR> px;
+  __device__ __forceinline__ void init(const WgradArgs& p, const WgBlock& blk) {
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+#pragma unroll
+    for (int j = 0; j < XI; ++j) {
+      const int r = (j * NW + wid) * RPX + lane / CPX;
+      const int kk = blk.k0 + wg_swz<BKK, MF>(r, (lane % CPX) * 8);
+      row[j] = r;
+      kok[j] = kk < p.K;
+      const int tap = kok[j] ? kk / p.C : 0;
+      ci[j] = kk - tap * p.C;
+      const int kh = tap / p.KW, kw = tap - (tap / p.KW) * p.KW;
+      ihb[j] = p.ih0 + kh * p.dh;
+      iwb[j] = p.iw0 + kw * p.dw;
+      px.seek(p, j, blk.mbeg + r);
+    }
+    px.init(p);
+  }
+  // LDS slot of piece j in stage `buf` of Xs ([stages][SR][BKK])
+  __device__ __forceinline__ const uint16_t* slot(const uint16_t* Xs, int buf, int j) const {
+    return Xs + buf * SR * BKK + (j * NW + (threadIdx.x >> 6)) * RPX * BKK;
+  }
+  __device__ __forceinline__ void issue(const WgradArgs& p, __amdgpu_buffer_rsrc_t rx,
+                                        const uint16_t* Xs, int it, int buf, const WgBlock& blk) {
+    const int mb = blk.mbeg + it * SR;
+#pragma unroll
+    for (int j = 0; j < XI; ++j) {
+      bool ok = mb + row[j] < blk.mend && kok[j];
+      dma16_opaque(rx, slot(Xs, buf, j), px.x_off(p, j, ihb[j], iwb[j], ci[j], ok));
+      px.advance(p, j);
+    }
+  }
+};
+
 // DEEP: operand loads run two 64-row steps ahead in two register sets (loop unrolled by two, every
 // set index static).  With one set the loads of step it+1 have only step it's MFMAs (~0.4 µs at
 // two waves per SIMD) to arrive, less than an L2 / MALL round trip under load: the layer3 3x3
@@ -1418,17 +1566,12 @@ __global__ __launch_bounds__(256, (BCO * BKK > 128 * 128) ? 1 : 2) void wgrad_tn
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wm = wid / WN, wn = wid % WN;
-  const int lbid = xcd_remap(blockIdx.x, gridDim.x);
-  const int tiles = p.nCo * p.nKk;
-  const int split = lbid / tiles;
-  const int tile = lbid % tiles;
-  const int co0 = (tile / p.nKk) * BCO;
-  const int k0 = (tile % p.nKk) * BKK;
+  const WgBlock blk = wg_block<BCO, BKK>(p);
+  const int split = blk.split, co0 = blk.co0, k0 = blk.k0;
+  const int mbeg = blk.mbeg, mend = blk.mend, nit = blk.nit;
 
-  const __amdgpu_buffer_rsrc_t rd_src =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.dY, (short)0, (int)p.dy_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rx_src =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.X, (short)0, (int)p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rd_src = buf_rsrc(p.dY, p.dy_bytes);
+  const __amdgpu_buffer_rsrc_t rx_src = buf_rsrc(p.X, p.x_bytes);
 
   // dY chunk owned by this thread
   const int dch = tid % CPD, drow = tid / CPD;
@@ -1442,7 +1585,6 @@ __global__ __launch_bounds__(256, (BCO * BKK > 128 * 128) ? 1 : 2) void wgrad_tn
   const int ci = kk - tap * p.C;
   const int kh = tap / p.KW;
   const int kw = tap - kh * p.KW;
-  const int OHW = p.OH * p.OW;
 
   struct Stage {
     u32x4 rd[DCH], rx[XCH], rd2[DCH];
@@ -1453,9 +1595,8 @@ __global__ __launch_bounds__(256, (BCO * BKK > 128 * 128) ? 1 : 2) void wgrad_tn
   // segments (views) a split may straddle the boundary, each dY row picks its set (host-checked:
   // dp_S <= 2, or every split inside one segment)
   float dA[8], dB[8], dD[8], dA1[8], dB1[8], dD1[8];
-  const __amdgpu_buffer_rsrc_t rd2_src = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(DPRO ? p.dY2 : p.dY), (short)0, (int)p.dy_bytes, 0x00020000);
-  const int dseg0 = DPRO ? (split * p.iters_per_split * 64) / p.dp_seg_rows : 0;
+  const __amdgpu_buffer_rsrc_t rd2_src = buf_rsrc(DPRO ? p.dY2 : p.dY, p.dy_bytes);
+  const int dseg0 = DPRO ? mbeg / p.dp_seg_rows : 0;
   const int dseg_next_row = (dseg0 + 1) * p.dp_seg_rows;  // first row of the next segment
   if (DPRO) {
     const int cc = dcol_ok ? dcol : 0;
@@ -1482,32 +1623,16 @@ __global__ __launch_bounds__(256, (BCO * BKK > 128 * 128) ? 1 : 2) void wgrad_tn
       psh1[e] = p.pro_S > 1 ? p.pro_sh[p.C + cc + e] : psh0[e];
     }
   }
-  const int mbeg = split * p.iters_per_split * 64;
-  const int mend_raw = mbeg + p.iters_per_split * 64;
-  const int mend = mend_raw < p.M ? mend_raw : p.M;
-  const int nit = (mend - mbeg + 63) / 64;
 
-  // Incremental im2col addressing: each thread's X rows advance by exactly 64 output pixels per
-  // iteration, so (n, oh, ow) are carried forward with compares instead of two integer
-  // divisions per chunk per iteration (those divisions were ~40 % of the loop's VALU work).
   const int ihb = p.ih0 + kh * p.dh, iwb = p.iw0 + kw * p.dw;
-  const int dn = 64 / OHW, dr = 64 - dn * OHW;
-  const int doh = dr / p.OW, dow = dr - doh * p.OW;
-  int xn[XCH], xoh[XCH], xow[XCH];
+  Im2colCursor<XCH, 64> px;
+  px.init(p);
 #pragma unroll
-  for (int j = 0; j < XCH; ++j) {
-    const int m = mbeg + xrow + RX * j;
-    const int n = m / OHW;
-    const int rem = m - n * OHW;
-    xn[j] = n;
-    xoh[j] = rem / p.OW;
-    xow[j] = rem - xoh[j] * p.OW;
-  }
+  for (int j = 0; j < XCH; ++j) px.seek(p, j, mbeg + xrow + RX * j);
   uint32_t doff[DCH];
 #pragma unroll
   for (int j = 0; j < DCH; ++j) doff[j] = (uint32_t)(((size_t)(mbeg + drow + RD * j) * p.N + dcol) * 2);
   const uint32_t dstep = (uint32_t)(64 * p.N * 2);
-  const int cstride = p.C * 2;
 
   auto gload = [&](int it, Stage& st) {
     const int mb = mbeg + it * 64;
@@ -1526,24 +1651,12 @@ __global__ __launch_bounds__(256, (BCO * BKK > 128 * 128) ? 1 : 2) void wgrad_tn
 #pragma unroll
     for (int j = 0; j < XCH; ++j) {
       const int m = mb + xrow + RX * j;
-      // 24-bit multiplies (full-rate v_mul_u32_u24): every factor is < 2^24 and the byte
-      // offset < 2^31 (host-checked), so the low 32 bits are exact
-      const int ih = (int)__umul24((unsigned)xoh[j], (unsigned)p.ish) + ihb;
-      const int iw = (int)__umul24((unsigned)xow[j], (unsigned)p.isw) + iwb;
-      const bool ok = m < mend && k_ok && (unsigned)ih < (unsigned)p.IH &&
-                      (unsigned)iw < (unsigned)p.IW;
+      bool ok = m < mend && k_ok;
+      const uint32_t off = px.x_off(p, j, ihb, iwb, ci, ok);
       st.xok[j] = ok;
       st.xseg[j] = pro && m >= p.pro_seg_rows;
-      const uint32_t pix =
-          __umul24(__umul24((unsigned)xn[j], (unsigned)p.IH) + (unsigned)ih, (unsigned)p.IW) +
-          (unsigned)iw;
-      const uint32_t off = ok ? __umul24(pix, (unsigned)cstride) + (uint32_t)(ci * 2) : p.x_bytes;
       st.rx[j] = __builtin_amdgcn_raw_buffer_load_b128(rx_src, off, 0, 0);
-      // advance this chunk's output pixel by 64 rows
-      int ow = xow[j] + dow, oh = xoh[j] + doh, n = xn[j] + dn;
-      if (ow >= p.OW) { ow -= p.OW; ++oh; }
-      if (oh >= p.OH) { oh -= p.OH; ++n; }
-      xow[j] = ow; xoh[j] = oh; xn[j] = n;
+      px.advance(p, j);
     }
   };
   auto lstore = [&](int buf, const Stage& st) {
@@ -1564,10 +1677,7 @@ __global__ __launch_bounds__(256, (BCO * BKK > 128 * 128) ? 1 : 2) void wgrad_tn
   };
 
   f32x4 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   if (nit > 0) {
     gload(0, S0);
@@ -1627,103 +1737,32 @@ template <int BCO, int BKK, int WM, int WN, bool PRO, int NST, int MF = 16>
 __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_glds(WgradArgs p) {
   static_assert(NST == 2 || NST == 3, "wgrad_glds stages");
   constexpr int NW = WM * WN;
-  constexpr int CPD = BCO / 8, RPD = 64 / CPD, DI = 64 / (RPD * NW);
-  constexpr int CPX = BKK / 8, RPX = 64 / CPX, XI = 64 / (RPX * NW);
-  static_assert(DI >= 1 && XI >= 1 && DI * RPD * NW == 64 && XI * RPX * NW == 64, "wgrad glds");
+  typedef WgDyLane<BCO, NW, 64, MF> DL;
+  typedef WgXLane<BKK, NW, 64, MF> XL;
+  constexpr int CPX = XL::CPX;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint16_t* Ds = (uint16_t*)smem;   // [2][64][BCO]
   uint16_t* Xs = Ds + NST * 64 * BCO;  // [NST][64][BKK]
   float* Pt = (float*)(Xs + NST * 64 * BKK);  // PRO: [sc, sh][segment 0, 1][BKK] of this k window
 
-  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  const int lbid = xcd_remap(blockIdx.x, gridDim.x);
-  const int tiles = p.nCo * p.nKk;
-  const int split = lbid / tiles;
-  const int tile = lbid % tiles;
-  const int co0 = (tile / p.nKk) * BCO;
-  const int k0 = (tile % p.nKk) * BKK;
-  const __amdgpu_buffer_rsrc_t rd =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.dY, (short)0, (int)p.dy_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.X, (short)0, (int)p.x_bytes, 0x00020000);
-  const int mbeg = split * p.iters_per_split * 64;
-  const int mend_raw = mbeg + p.iters_per_split * 64;
-  const int mend = mend_raw < p.M ? mend_raw : p.M;
-  const int nit = mend > mbeg ? (mend - mbeg + 63) / 64 : 0;
-  const int OHW = p.OH * p.OW;
-
-  // dY: lane → (row in piece, physical chunk) → logical column chunk
-  int d_row[DI];
-  uint32_t d_off[DI];
-  bool d_cok[DI];
-#pragma unroll
-  for (int j = 0; j < DI; ++j) {
-    const int r = (j * NW + wid) * RPD + lane / CPD;
-    const int col = co0 + wg_swz<BCO, MF>(r, (lane % CPD) * 8);
-    d_row[j] = r;
-    d_cok[j] = col < p.N;
-    d_off[j] = (uint32_t)(((size_t)(mbeg + r) * p.N + col) * 2);
-  }
-  const uint32_t dstep = (uint32_t)(64 * p.N * 2);
-  // X: fixed (tap, channel) per lane and piece; output pixel carried incrementally
-  int x_row[XI], x_ci[XI], x_ihb[XI], x_iwb[XI], xn[XI], xoh[XI], xow[XI];
-  bool x_kok[XI];
-#pragma unroll
-  for (int j = 0; j < XI; ++j) {
-    const int r = (j * NW + wid) * RPX + lane / CPX;
-    const int kk = k0 + wg_swz<BKK, MF>(r, (lane % CPX) * 8);
-    x_row[j] = r;
-    x_kok[j] = kk < p.K;
-    const int tap = x_kok[j] ? kk / p.C : 0;
-    x_ci[j] = kk - tap * p.C;
-    const int kh = tap / p.KW, kw = tap - (tap / p.KW) * p.KW;
-    x_ihb[j] = p.ih0 + kh * p.dh;
-    x_iwb[j] = p.iw0 + kw * p.dw;
-    const int m = mbeg + r;
-    xn[j] = m / OHW;
-    const int rem = m - xn[j] * OHW;
-    xoh[j] = rem / p.OW;
-    xow[j] = rem - xoh[j] * p.OW;
-  }
-  const int dn = 64 / OHW, dr = 64 - dn * OHW;
-  const int doh = dr / p.OW, dow = dr - doh * p.OW;
-  const int cstride = p.C * 2;
-
+  const int tid = threadIdx.x;
+  const WgBlock blk = wg_block<BCO, BKK>(p);
+  const int k0 = blk.k0, mbeg = blk.mbeg, nit = blk.nit;
+  const __amdgpu_buffer_rsrc_t rd = buf_rsrc(p.dY, p.dy_bytes);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(p.X, p.x_bytes);
+  DL dl;
+  XL xl;
+  dl.init(p, blk);
+  xl.init(p, blk);
   auto issue = [&](int it, int buf) {
-    const int mb = mbeg + it * 64;
-#pragma unroll
-    for (int j = 0; j < DI; ++j) {
-      const bool ok = mb + d_row[j] < mend && d_cok[j];
-      dma16_opaque(rd, Ds + buf * 64 * BCO + (j * NW + wid) * RPD * BCO,
-                   ok ? d_off[j] : p.dy_bytes);
-      d_off[j] += dstep;
-    }
-#pragma unroll
-    for (int j = 0; j < XI; ++j) {
-      const int ih = (int)__umul24((unsigned)xoh[j], (unsigned)p.ish) + x_ihb[j];
-      const int iw = (int)__umul24((unsigned)xow[j], (unsigned)p.isw) + x_iwb[j];
-      const bool ok = mb + x_row[j] < mend && x_kok[j] && (unsigned)ih < (unsigned)p.IH &&
-                      (unsigned)iw < (unsigned)p.IW;
-      const uint32_t pix =
-          __umul24(__umul24((unsigned)xn[j], (unsigned)p.IH) + (unsigned)ih, (unsigned)p.IW) +
-          (unsigned)iw;
-      const uint32_t off = ok ? __umul24(pix, (unsigned)cstride) + (uint32_t)(x_ci[j] * 2)
-                              : p.x_bytes;
-      dma16_opaque(rx, Xs + buf * 64 * BKK + (j * NW + wid) * RPX * BKK, off);
-      int ow = xow[j] + dow, oh = xoh[j] + doh, n = xn[j] + dn;
-      if (ow >= p.OW) { ow -= p.OW; ++oh; }
-      if (oh >= p.OH) { oh -= p.OH; ++n; }
-      xow[j] = ow; xoh[j] = oh; xn[j] = n;
-    }
+    dl.issue(p, rd, Ds, it, buf, blk);
+    xl.issue(p, rx, Xs, it, buf, blk);
   };
 
   typename WMfma<MF>::acc_t acc[BCO / WM / MF][BKK / WN / MF];
-#pragma unroll
-  for (int i = 0; i < BCO / WM / MF; ++i)
-#pragma unroll
-    for (int j = 0; j < BKK / WN / MF; ++j) acc[i][j] = {};
+  zero_acc(acc);
 
-  constexpr int PER = DI + XI;  // DMA instructions per wave per step
+  constexpr int PER = DL::DI + XL::XI;  // DMA instructions per wave per step
   if (PRO) {
     // the prologue's per-channel table is staged in LDS before any DMA is issued: an ordinary
     // global load consumed inside the loop would make hipcc drain the DMA queue (vmcnt(0))
@@ -1816,7 +1855,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_glds(WgradArgs p) {
     }
     if (WG_CUT != 2) wgrad_mma<BCO, BKK, WM, WN, 2, MF>(Ds + cur * 64 * BCO, Xs + cur * 64 * BKK, acc);
   }
-  wgrad_store<BCO, BKK, WM, WN, MF>(p, acc, split, co0, k0);
+  wgrad_store<BCO, BKK, WM, WN, MF>(p, acc, blk.split, blk.co0, k0);
 }
 
 // Weight-gradient fragments of one k sub-step (32 rows at MF 16, 16 rows at MF 32) of one wave
@@ -1889,125 +1928,57 @@ __device__ __forceinline__ void wg_mma_ks(const WgKs<TCO, TKK, MF>& f,
 template <int BCO, int BKK, int WM, int WN, int MF, bool XLIN = false>
 __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_xp(WgradArgs p) {
   constexpr int NW = WM * WN;
-  constexpr int CPD = BCO / 8, RPD = 64 / CPD, DI = 64 / (RPD * NW);
-  constexpr int CPX = BKK / 8, RPX = 64 / CPX, XI = 64 / (RPX * NW);
-  static_assert(DI >= 1 && XI >= 1 && DI * RPD * NW == 64 && XI * RPX * NW == 64, "wgrad xp");
-  constexpr int PER = DI + XI;
+  typedef WgDyLane<BCO, NW, 64, MF> DL;
+  typedef WgXLane<BKK, NW, 64, MF> XL;
+  constexpr int XI = XL::XI, PER = DL::DI + XI;
   constexpr int TCO = BCO / WM, TKK = BKK / WN;
   constexpr int NSUB = MF == 16 ? 2 : 4;  // k sub-steps per 64-row step (even: f[0] restarts)
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint16_t* Ds = (uint16_t*)smem;       // [2][64][BCO]
   uint16_t* Xs = Ds + 2 * 64 * BCO;     // [2][64][BKK]
 
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int wid = threadIdx.x >> 6;
   const int co_w = (wid / WN) * TCO, kk_w = (wid % WN) * TKK;
-  const int lbid = xcd_remap(blockIdx.x, gridDim.x);
-  const int tiles = p.nCo * p.nKk;
-  const int split = lbid / tiles;
-  const int tile = lbid % tiles;
-  const int co0 = (tile / p.nKk) * BCO;
-  const int k0 = (tile % p.nKk) * BKK;
-  const __amdgpu_buffer_rsrc_t rd =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.dY, (short)0, (int)p.dy_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.X, (short)0, (int)p.x_bytes, 0x00020000);
-  const int mbeg = split * p.iters_per_split * 64;
-  const int mend_raw = mbeg + p.iters_per_split * 64;
-  const int mend = mend_raw < p.M ? mend_raw : p.M;
-  const int nit = mend > mbeg ? (mend - mbeg + 63) / 64 : 0;
-  const int OHW = p.OH * p.OW;
-
-  int d_row[DI];
-  uint32_t d_off[DI];
-  bool d_cok[DI];
-#pragma unroll
-  for (int j = 0; j < DI; ++j) {
-    const int r = (j * NW + wid) * RPD + lane / CPD;
-    const int col = co0 + wg_swz<BCO, MF>(r, (lane % CPD) * 8);
-    d_row[j] = r;
-    d_cok[j] = col < p.N;
-    d_off[j] = (uint32_t)(((size_t)(mbeg + r) * p.N + col) * 2);
-  }
-  const uint32_t dstep = (uint32_t)(64 * p.N * 2);
-  int x_row[XI], x_ci[XI], x_ihb[XI], x_iwb[XI], xn[XI], xoh[XI], xow[XI];
-  bool x_kok[XI];
-#pragma unroll
-  for (int j = 0; j < XI; ++j) {
-    const int r = (j * NW + wid) * RPX + lane / CPX;
-    const int kk = k0 + wg_swz<BKK, MF>(r, (lane % CPX) * 8);
-    x_row[j] = r;
-    x_kok[j] = kk < p.K;
-    const int tap = x_kok[j] ? kk / p.C : 0;
-    x_ci[j] = kk - tap * p.C;
-    const int kh = tap / p.KW, kw = tap - (tap / p.KW) * p.KW;
-    x_ihb[j] = p.ih0 + kh * p.dh;
-    x_iwb[j] = p.iw0 + kw * p.dw;
-    const int m = mbeg + r;
-    xn[j] = m / OHW;
-    const int rem = m - xn[j] * OHW;
-    xoh[j] = rem / p.OW;
-    xow[j] = rem - xoh[j] * p.OW;
-  }
-  const int dn = 64 / OHW, dr = 64 - dn * OHW;
-  const int doh = dr / p.OW, dow = dr - doh * p.OW;
-  const int cstride = p.C * 2;
+  const WgBlock blk = wg_block<BCO, BKK>(p);
+  const int nit = blk.nit;
+  const __amdgpu_buffer_rsrc_t rd = buf_rsrc(p.dY, p.dy_bytes);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(p.X, p.x_bytes);
+  DL dl;
+  XL xl;
+  dl.init(p, blk);
+  xl.init(p, blk);
   uint32_t xl_off[XLIN ? XI : 1];
   bool xl_ok[XLIN ? XI : 1];
   if constexpr (XLIN) {
+    const int cstride = p.C * 2;
 #pragma unroll
     for (int j = 0; j < XI; ++j) {
-      const int ih = xoh[j] * p.ish + x_ihb[j];
-      const int iw = xow[j] * p.isw + x_iwb[j];
-      xl_ok[j] = x_kok[j] && (unsigned)ih < (unsigned)p.IH && (unsigned)iw < (unsigned)p.IW;
-      xl_off[j] = xl_ok[j] ? (uint32_t)((((size_t)xn[j] * p.IH + ih) * p.IW + iw) * cstride +
-                                        x_ci[j] * 2)
+      const int ih = xl.px.oh[j] * p.ish + xl.ihb[j];
+      const int iw = xl.px.ow[j] * p.isw + xl.iwb[j];
+      xl_ok[j] = xl.kok[j] && (unsigned)ih < (unsigned)p.IH && (unsigned)iw < (unsigned)p.IW;
+      xl_off[j] = xl_ok[j] ? (uint32_t)((((size_t)xl.px.n[j] * p.IH + ih) * p.IW + iw) * cstride +
+                                        xl.ci[j] * 2)
                            : 0u;
     }
   }
 
   auto issue = [&](int it, int buf) {
-    const int mb = mbeg + it * 64;
-#pragma unroll
-    for (int j = 0; j < DI; ++j) {
-      const bool ok = mb + d_row[j] < mend && d_cok[j];
-      dma16_opaque(rd, Ds + buf * 64 * BCO + (j * NW + wid) * RPD * BCO,
-                   ok ? d_off[j] : p.dy_bytes);
-      d_off[j] += dstep;
-    }
+    dl.issue(p, rd, Ds, it, buf, blk);
     if constexpr (XLIN) {
+      const int mb = blk.mbeg + it * 64;
 #pragma unroll
       for (int j = 0; j < XI; ++j) {
-        const bool ok = mb + x_row[j] < mend && xl_ok[j];
-        dma16_opaque(rx, Xs + buf * 64 * BKK + (j * NW + wid) * RPX * BKK,
-                     ok ? xl_off[j] : p.x_bytes);
+        const bool ok = mb + xl.row[j] < blk.mend && xl_ok[j];
+        dma16_opaque(rx, xl.slot(Xs, buf, j), ok ? xl_off[j] : p.x_bytes);
         xl_off[j] += p.x_step;
       }
-      return;
-    }
-#pragma unroll
-    for (int j = 0; j < XI; ++j) {
-      const int ih = (int)__umul24((unsigned)xoh[j], (unsigned)p.ish) + x_ihb[j];
-      const int iw = (int)__umul24((unsigned)xow[j], (unsigned)p.isw) + x_iwb[j];
-      const bool ok = mb + x_row[j] < mend && x_kok[j] && (unsigned)ih < (unsigned)p.IH &&
-                      (unsigned)iw < (unsigned)p.IW;
-      const uint32_t pix =
-          __umul24(__umul24((unsigned)xn[j], (unsigned)p.IH) + (unsigned)ih, (unsigned)p.IW) +
-          (unsigned)iw;
-      const uint32_t off = ok ? __umul24(pix, (unsigned)cstride) + (uint32_t)(x_ci[j] * 2)
-                              : p.x_bytes;
-      dma16_opaque(rx, Xs + buf * 64 * BKK + (j * NW + wid) * RPX * BKK, off);
-      int ow = xow[j] + dow, oh = xoh[j] + doh, n = xn[j] + dn;
-      if (ow >= p.OW) { ow -= p.OW; ++oh; }
-      if (oh >= p.OH) { oh -= p.OH; ++n; }
-      xow[j] = ow; xoh[j] = oh; xn[j] = n;
+    } else {
+      xl.issue(p, rx, Xs, it, buf, blk);
     }
   };
 
   typename WMfma<MF>::acc_t acc[TCO / MF][TKK / MF];
-#pragma unroll
-  for (int i = 0; i < TCO / MF; ++i)
-#pragma unroll
-    for (int j = 0; j < TKK / MF; ++j) acc[i][j] = {};
+  zero_acc(acc);
   WgKs<TCO, TKK, MF> f[2];  // rolling pair: sub-step j + 1 is read while sub-step j multiplies
 
   if (nit > 0) {
@@ -2045,7 +2016,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_xp(WgradArgs p) {
       wg_mma_ks<TCO, TKK, MF>(f[j & 1], acc);
     }
   }
-  wgrad_store_at<TCO, TKK, MF>(p, acc, split, co0 + co_w, k0 + kk_w);
+  wgrad_store_at<TCO, TKK, MF>(p, acc, blk.split, blk.co0 + co_w, blk.k0 + kk_w);
 }
 
 // Deep-pipelined LDS-DMA weight gradient (no operand prologues).  wgrad_glds stages 64-row
@@ -2079,10 +2050,8 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_pipe(WgradArgs p) {
   const int tile = lbid % tiles;
   const int co0 = (tile / p.nKk) * BCO;
   const int k0 = (tile % p.nKk) * BKK;
-  const __amdgpu_buffer_rsrc_t rd =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.dY, (short)0, (int)p.dy_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.X, (short)0, (int)p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rd = buf_rsrc(p.dY, p.dy_bytes);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(p.X, p.x_bytes);
   const int mbeg = split * p.iters_per_split * 64;  // host splits in 64-row units
   const int mend_raw = mbeg + p.iters_per_split * 64;
   const int mend = mend_raw < p.M ? mend_raw : p.M;
@@ -2153,10 +2122,7 @@ __global__ __launch_bounds__(64 * WM * WN, 1) void wgrad_pipe(WgradArgs p) {
   };
 
   typename WMfma<MF>::acc_t acc[BCO / WM / MF][BKK / WN / MF];
-#pragma unroll
-  for (int i = 0; i < BCO / WM / MF; ++i)
-#pragma unroll
-    for (int j = 0; j < BKK / WN / MF; ++j) acc[i][j] = {};
+  zero_acc(acc);
 
 #pragma unroll
   for (int j = 0; j < NST - 1; ++j)
@@ -2219,10 +2185,8 @@ __global__ __launch_bounds__(576, 1) void wgrad_patch(WgradArgs p) {
   const int t_beg = split * p.iters_per_split;
   const int t_end = min(ntot, t_beg + p.iters_per_split);
   const int OHW = p.OH * OW;
-  const __amdgpu_buffer_rsrc_t rd =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.dY, (short)0, (int)p.dy_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.X, (short)0, (int)p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rd = buf_rsrc(p.dY, p.dy_bytes);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(p.X, p.x_bytes);
   const int lr = lane >> 3, lpc = lane & 7;
 
   auto issue = [&](int t, int buf) {
@@ -2247,10 +2211,7 @@ __global__ __launch_bounds__(576, 1) void wgrad_patch(WgradArgs p) {
   };
 
   f32x4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   // PRO: the [S<=2][sc, sh][64] table of this block's input-channel slice, staged in LDS behind
   // the two stages BEFORE any DMA (global loads consumed inside the loop would make hipcc drain
   // the in-flight opaque DMA with vmcnt(0); tools/isa_check.py)
@@ -2684,32 +2645,40 @@ void launch_patch(const IgemmArgs& a, hipStream_t s) {
   }, kFusionPairs);
 }
 
+// Calls f with every runtime bool turned into a std::bool_constant argument, so that f can name
+// the kernel instantiation the bools select.
+template <class F>
+void with_bools(F&& f) { f(); }
+template <class F, class... Bs>
+void with_bools(F&& f, bool b, Bs... rest) {
+  if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
+// Stores the tile counts of a launch with bco x bkk tiles over N x kcols for the kernels' block
+// decode (wg_block) and returns its grid: one block per (split, tile).
+inline int wgrad_grid(WgradArgs& a, int bco, int bkk, int kcols) {
+  a.nCo = (a.N + bco - 1) / bco;
+  a.nKk = (kcols + bkk - 1) / bkk;
+  return a.nCo * a.nKk * a.splits;
+}
+
 template <int BCO, int BKK, int WM, int WN, bool DEEP = false>
 void launch_wgrad(const WgradArgs& a0, hipStream_t s) {
-  const bool pro = a0.pro_sc != nullptr;
-  const bool dpro = a0.dY2 != nullptr;
   WgradArgs a = a0;
-  a.nCo = (a.N + BCO - 1) / BCO;
-  a.nKk = (a.K + BKK - 1) / BKK;
-  const int grid = a.nCo * a.nKk * a.splits;
+  const int grid = wgrad_grid(a, BCO, BKK, a.K);
   const size_t lds = (size_t)2 * 64 * (BCO + BKK) * 2;
-  if (pro && dpro)
-    hipLaunchKernelGGL((wgrad_tn<BCO, BKK, WM, WN, true, true, DEEP>), dim3(grid), dim3(256), lds, s, a);
-  else if (pro)
-    hipLaunchKernelGGL((wgrad_tn<BCO, BKK, WM, WN, true, false, DEEP>), dim3(grid), dim3(256), lds, s, a);
-  else if (dpro)
-    hipLaunchKernelGGL((wgrad_tn<BCO, BKK, WM, WN, false, true, DEEP>), dim3(grid), dim3(256), lds, s, a);
-  else
-    hipLaunchKernelGGL((wgrad_tn<BCO, BKK, WM, WN, false, false, DEEP>), dim3(grid), dim3(256), lds, s, a);
+  with_bools([&](auto pro, auto dpro) {
+    hipLaunchKernelGGL((wgrad_tn<BCO, BKK, WM, WN, decltype(pro)::value, decltype(dpro)::value, DEEP>),
+                       dim3(grid), dim3(256), lds, s, a);
+  }, a.pro_sc != nullptr, a.dY2 != nullptr);
   HIP_CHECK_LAUNCH();
 }
 
 template <int BCO, int BKK, int WM, int WN, int SR, int NST, int MF = 16>
 void launch_wgrad_pipe(const WgradArgs& a0, hipStream_t s) {
   WgradArgs a = a0;
-  a.nCo = (a.N + BCO - 1) / BCO;
-  a.nKk = (a.K + BKK - 1) / BKK;
-  const int grid = a.nCo * a.nKk * a.splits;
+  const int grid = wgrad_grid(a, BCO, BKK, a.K);
   const size_t lds = (size_t)NST * SR * (BCO + BKK) * 2;
   hipLaunchKernelGGL((wgrad_pipe<BCO, BKK, WM, WN, SR, NST, MF>), dim3(grid), dim3(64 * WM * WN),
                      lds, s, a);
@@ -2746,54 +2715,38 @@ inline uint32_t wgrad_x_linear(const WgradArgs& a) {
 template <int BCO, int BKK, int WM, int WN, int MF>
 void launch_wgrad_xp(const WgradArgs& a0, hipStream_t s) {
   WgradArgs a = a0;
-  a.nCo = (a.N + BCO - 1) / BCO;
-  a.nKk = (a.K + BKK - 1) / BKK;
-  const int grid = a.nCo * a.nKk * a.splits;
+  const int grid = wgrad_grid(a, BCO, BKK, a.K);
   const size_t lds = (size_t)2 * 64 * (BCO + BKK) * 2;
   a.x_step = wgrad_x_linear(a);
-  if (a.x_step != 0)
-    hipLaunchKernelGGL((wgrad_xp<BCO, BKK, WM, WN, MF, true>), dim3(grid), dim3(64 * WM * WN), lds,
-                       s, a);
-  else
-    hipLaunchKernelGGL((wgrad_xp<BCO, BKK, WM, WN, MF>), dim3(grid), dim3(64 * WM * WN), lds, s, a);
+  with_bools([&](auto xlin) {
+    hipLaunchKernelGGL((wgrad_xp<BCO, BKK, WM, WN, MF, decltype(xlin)::value>), dim3(grid),
+                       dim3(64 * WM * WN), lds, s, a);
+  }, a.x_step != 0);
   HIP_CHECK_LAUNCH();
 }
 
 template <int BCO, int BKK, int WM, int WN, int NST = 2, int MF = 16>
 void launch_wgrad_glds(const WgradArgs& a0, hipStream_t s) {
   WgradArgs a = a0;
-  a.nCo = (a.N + BCO - 1) / BCO;
-  a.nKk = (a.K + BKK - 1) / BKK;
-  const int grid = a.nCo * a.nKk * a.splits;
+  const int grid = wgrad_grid(a, BCO, BKK, a.K);
   const size_t lds = (size_t)NST * 64 * (BCO + BKK) * 2 + (a.pro_sc != nullptr ? 16 * BKK : 0);
-  if (a.pro_sc != nullptr)
-    hipLaunchKernelGGL((wgrad_glds<BCO, BKK, WM, WN, true, NST, MF>), dim3(grid), dim3(64 * WM * WN),
-                       lds, s, a);
-  else
-    hipLaunchKernelGGL((wgrad_glds<BCO, BKK, WM, WN, false, NST, MF>), dim3(grid), dim3(64 * WM * WN),
-                       lds, s, a);
+  with_bools([&](auto pro) {
+    hipLaunchKernelGGL((wgrad_glds<BCO, BKK, WM, WN, decltype(pro)::value, NST, MF>), dim3(grid),
+                       dim3(64 * WM * WN), lds, s, a);
+  }, a.pro_sc != nullptr);
   HIP_CHECK_LAUNCH();
 }
 
 void launch_wgrad_patch(const WgradArgs& a0, hipStream_t s) {
   WgradArgs a = a0;
-  a.nCo = a.N / 64;
-  a.nKk = a.C / 64;
+  const int grid = wgrad_grid(a, 64, 64, a.C);  // N % 64 == 0 and C % 64 == 0 (wgrad_variant_ok)
   const int pp = (256 / a.OW + 2) * (a.OW + 2);
   const size_t lds = (size_t)2 * (256 * 64 + (pp + 7) / 8 * 512) * 2 +
                      (a.pro_sc != nullptr ? (size_t)2 * 2 * 64 * 4 : 0);
-  const dim3 grid(a.nCo * a.nKk * a.splits);
-  if (a.OW == 32) {
-    if (a.pro_sc != nullptr)
-      hipLaunchKernelGGL((wgrad_patch<true, 32>), grid, dim3(576), lds, s, a);
-    else
-      hipLaunchKernelGGL((wgrad_patch<false, 32>), grid, dim3(576), lds, s, a);
-  } else {
-    if (a.pro_sc != nullptr)
-      hipLaunchKernelGGL((wgrad_patch<true, 16>), grid, dim3(576), lds, s, a);
-    else
-      hipLaunchKernelGGL((wgrad_patch<false, 16>), grid, dim3(576), lds, s, a);
-  }
+  with_bools([&](auto pro, auto ow32) {
+    hipLaunchKernelGGL((wgrad_patch<decltype(pro)::value, decltype(ow32)::value ? 32 : 16>),
+                       dim3(grid), dim3(576), lds, s, a);
+  }, a.pro_sc != nullptr, a.OW == 32);
   HIP_CHECK_LAUNCH();
 }
 
@@ -2973,12 +2926,9 @@ __global__ __launch_bounds__(256, 1) void conv1x1_bwd_dual(Dual1x1Args p) {
   const int T = p.tiles_per_block;
   const bool lazy = p.A3 != nullptr;
 
-  const __amdgpu_buffer_rsrc_t rg =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.G, (short)0, (int)p.g_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(lazy ? p.A3 : p.G), (short)0, (int)p.g_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rx =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.X, (short)0, (int)p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(p.G, p.g_bytes);
+  const __amdgpu_buffer_rsrc_t ra = buf_rsrc(lazy ? p.A3 : p.G, p.g_bytes);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc(p.X, p.x_bytes);
 
   // W^T resident for the whole block (one 32 KB read per block)
   for (int c = tid; c < CI * CO / 8; c += 256) {
@@ -3235,13 +3185,10 @@ __global__ __launch_bounds__(512, 1) void conv1x1_bwd_dual_w(Dual1x1Args p) {
   const int mbeg = seg * p.seg_rows + (blk - seg * p.bps) * p.tiles_per_block * BMT;
   const int T = p.tiles_per_block;
 
-  const __amdgpu_buffer_rsrc_t rg =
-      __builtin_amdgcn_make_buffer_rsrc((void*)p.G, (short)0, (int)p.g_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(LAZY ? p.A3 : p.G), (short)0, (int)p.g_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rg = buf_rsrc(p.G, p.g_bytes);
+  const __amdgpu_buffer_rsrc_t ra = buf_rsrc(LAZY ? p.A3 : p.G, p.g_bytes);
   // XPRE: threads 256.. load the raw a2 chunk the thread 256 below loads the transformed one of
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)((XPRE && wid >= 4) ? p.Xraw : p.X), (short)0, (int)p.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = buf_rsrc((XPRE && wid >= 4) ? p.Xraw : p.X, p.x_bytes);
 
   for (int c = tid; c < CI * CO / 8; c += NT) {
     const int row = c / (CO / 8), ch = c % (CO / 8);

@@ -523,6 +523,39 @@ def test_wgrad_glds_variants(ops, k, s, p, C, Co, H, xlin):
         ops.wgrad_xlin(prev)
 
 
+@pytest.mark.parametrize("k,p,C,Co", [(3, 1, 64, 64), (1, 0, 64, 256)])
+@pytest.mark.parametrize("xlin", [0, 1])
+def test_wgrad_empty_trailing_splits(ops, k, p, C, Co, xlin):
+    """Splits with no rows: M = 8 * 8 * 8 = 512 is 8 steps of 64 rows, so 7 splits take 2 steps
+    each and splits 4-6 are empty (5 and 6 begin past M).  Every admissible variant must issue
+    nothing for them and store a zero slab, and the sum must match torch's fp32 weight gradient.
+    (An 8-wide output excludes the patch variant, which counts its splits in 256-row tiles.)"""
+    from simclr_amd.ops.conv_hip import fwd_geom
+    torch.manual_seed(29)
+    N, H, splits = 8, 8, 7
+    x = _bf(torch.randn(N, C, H, H, device=DEV))
+    wr = (_bf(torch.randn(Co, C, k, k, device=DEV)) * 0.05).float().requires_grad_(True)
+    y = F.conv2d(x.float(), wr, None, 1, p)
+    gy = _bf(torch.randn_like(y))
+    y.backward(gy.float())
+    g = fwd_geom(N, H, H, C, H, H, k, k, 1, p, Co)
+    xn = x.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+    dyn = gy.contiguous(memory_format=torch.channels_last).permute(0, 2, 3, 1)
+    K = k * k * C
+    vs = [v for v in range(ops.wgrad_nvariants()) if ops.wgrad_variant_ok(v, g, False, False)]
+    assert vs
+    prev = ops.wgrad_xlin(-1)
+    assert ops.wgrad_xlin(xlin) == xlin
+    try:
+        for v in vs:
+            part = torch.full((splits * Co * K,), float("nan"), device=DEV)
+            out = torch.empty(Co, k, k, C, device=DEV)
+            ops.wgrad(dyn, xn, part, out, g, splits, C, 0.0, None, None, 0, False, 1, v)
+            assert _rel(out.permute(0, 3, 1, 2), wr.grad) < 1e-2, v
+    finally:
+        ops.wgrad_xlin(prev)
+
+
 @pytest.mark.parametrize("k,p,C,Co,H", [(3, 1, 128, 128, 16), (3, 1, 64, 128, 32),
                                         (1, 0, 128, 256, 16), (3, 1, 256, 256, 8)])
 def test_igemm_dgrad_parity_classes_every_variant(ops, k, p, C, Co, H):
