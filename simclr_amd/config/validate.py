@@ -23,9 +23,21 @@ def _check_blur(cfg) -> None:
     _check(ks <= MAX_BLUR_KERNEL, f"data.blur_kernel must be <= {MAX_BLUR_KERNEL}")
 
 
+def _check_supervised(cfg) -> None:
+    """The opt-in ``loss.supervised`` (SupCon, loss/ntxent.py): a boolean; not with the ring."""
+    loss = (cfg.get("loss") if hasattr(cfg, "get") else None) or {}
+    sup = loss.get("supervised")
+    if sup is None:
+        return
+    _check(isinstance(sup, bool), "loss.supervised must be a boolean")
+    _check(not (sup and str(loss.get("gather")).lower() == "ring"),
+           "loss.supervised=true is not available with loss.gather=ring")
+
+
 def check_pretrain_conf(cfg) -> None:
     p, e = cfg["parameter"], cfg["experiment"]
     _check_blur(cfg)
+    _check_supervised(cfg)
     _check(p["temperature"] > 0.0, "parameter.temperature must be > 0")
     _check(p["epochs"] > 0, "parameter.epochs must be > 0")
     _check(e["batches"] > 0, "experiment.batches must be > 0")

@@ -868,6 +868,72 @@ void nt_reduce_loss(const Tensor& loss_rows, double scale, const Tensor& out) {
   ntxent_reduce_loss(f32(loss_rows, "loss_rows"), loss_rows.numel(), (float)scale, f32w(out, "out"),
                      cur_stream());
 }
+// ---- label mode (SupCon): ycol = the columns' int32 labels
+// ycol covers the columns [y0, y0 + len): the scored window and the rank's own rows lie inside
+void nt_sup_forward_range(const Tensor& znT, const Tensor& ycol, int64_t y0, int64_t R,
+                          int64_t col_offset, int64_t n_local, double inv_temp, const Tensor& part,
+                          int64_t c_lo, int64_t c_hi, int64_t splits, int64_t split_base) {
+  const int D = znT.size(0), Ccols = znT.size(1);
+  check_nt(R, Ccols, D, col_offset, n_local);
+  TORCH_CHECK(c_lo >= 0 && c_lo < c_hi && c_hi <= Ccols && c_lo % 16 == 0 && c_hi % 16 == 0 &&
+                  splits >= 1 && split_base >= 0 && part.numel() >= (split_base + splits) * R * 4,
+              "nt_sup_forward_range: column window / splits");
+  const int* y = i32(ycol, "nt_sup_forward_range: ycol");
+  const int64_t y1 = y0 + ycol.numel();
+  TORCH_CHECK(y0 >= 0 && y0 % 16 == 0 && y1 <= Ccols && y0 <= c_lo && c_hi <= y1 &&
+                  y0 <= col_offset && col_offset + R <= y1,
+              "nt_sup_forward_range: ycol holds the labels of columns [", y0, ", ", y1,
+              "), which must cover the window [", c_lo, ", ", c_hi, ") and the rows' own columns [",
+              col_offset, ", ", col_offset + R, ")");
+  supcon_forward_range(f32(znT, "znT"), y, y0, R, Ccols, D, col_offset, (float)inv_temp,
+                       f32w(part, "part"), c_lo, c_hi, splits, split_base, cur_stream());
+}
+void nt_sup_finish(const Tensor& part, int64_t R, int64_t splits, const Tensor& lse,
+                   const Tensor& inv_cnt, const Tensor& loss) {
+  TORCH_CHECK(part.numel() >= splits * R * 4 && lse.numel() == R && inv_cnt.numel() == R &&
+                  loss.numel() == R, "nt_sup_finish sizes");
+  supcon_finish(f32(part, "part"), R, splits, f32w(lse, "lse"), f32w(inv_cnt, "inv_cnt"),
+                f32w(loss, "loss"), cur_stream());
+}
+void nt_sup_backward_part(bool row_mode, const Tensor& zn, const Tensor& znT, const Tensor& lse,
+                          const Tensor& inv_cnt, const Tensor& ycol, int64_t R, int64_t col_offset,
+                          int64_t n_local, double inv_temp, double gscale,
+                          const c10::optional<Tensor>& gout, const Tensor& part, int64_t splits,
+                          const Tensor& out) {
+  const int D = znT.size(0), Ccols = znT.size(1);
+  check_nt(R, Ccols, D, col_offset, n_local);
+  TORCH_CHECK(zn.numel() == (int64_t)Ccols * D, "nt_sup_backward: zn size");
+  TORCH_CHECK(lse.numel() == R && inv_cnt.numel() == R, "nt_sup_backward: lse / inv_cnt size");
+  const int* y = i32(ycol, "nt_sup_backward: ycol");
+  TORCH_CHECK(ycol.numel() == Ccols, "nt_sup_backward: ycol must hold one label per column (",
+              Ccols, "), got ", ycol.numel());
+  const int64_t nown = row_mode ? R : Ccols;
+  TORCH_CHECK(splits >= 1 && part.numel() >= splits * nown * D && out.numel() == nown * D,
+              "nt_sup_backward sizes");
+  supcon_backward_part(row_mode ? 1 : 0, f32(zn, "zn"), f32(znT, "znT"), f32(lse, "lse"),
+                       f32(inv_cnt, "inv_cnt"), y, R, Ccols, D, col_offset, (float)inv_temp,
+                       (float)gscale, optf32(gout, "gout"), f32w(part, "part"), splits,
+                       f32w(out, "out"), cur_stream());
+}
+// out [views * n] int32 = labels[idx] (or labels itself, n of them) repeated once per view
+void nt_expand_labels(const Tensor& labels, const c10::optional<Tensor>& idx, int64_t views,
+                      const Tensor& out) {
+  TORCH_CHECK(labels.is_cuda() && labels.is_contiguous() && labels.dim() == 1 &&
+                  (labels.scalar_type() == at::kInt || labels.scalar_type() == at::kLong),
+              "nt_expand_labels: labels must be a contiguous 1-D int32 or int64 GPU tensor, got ",
+              labels.scalar_type());
+  const bool has_idx = idx.has_value() && idx->defined();
+  if (has_idx) check_dev(*idx, at::kLong, "nt_expand_labels: idx");
+  const int64_t n = has_idx ? idx->numel() : labels.numel();
+  TORCH_CHECK(views >= 1 && n >= 1 && labels.numel() >= 1 && views * n < (1LL << 31),
+              "nt_expand_labels: empty input");
+  check_dev(out, at::kInt, "nt_expand_labels: out");
+  TORCH_CHECK(out.numel() == views * n, "nt_expand_labels: out must hold views * n = ", views * n,
+              " labels, got ", out.numel());
+  supcon_expand_labels(labels.data_ptr(), labels.scalar_type() == at::kLong ? 1 : 0,
+                       has_idx ? idx->data_ptr<int64_t>() : nullptr, labels.numel(), (int)n,
+                       (int)views, out.data_ptr<int>(), cur_stream());
+}
 
 // ------------------------------------------------------------------------------- lars
 void lars_norms_op(const Tensor& p, const Tensor& g, const Tensor& chunk_beg,
@@ -1340,6 +1406,10 @@ TORCH_LIBRARY(simclr_amd, m) {
   m.def("nt_backward_part(bool row_mode, Tensor zn, Tensor znT, Tensor lse, int R, int col_offset, int n_local, float inv_temp, float gscale, Tensor? gout, Tensor(a!) part, int splits, Tensor(b!) out) -> ()", &nt_backward_part);
   m.def("nt_normalize_backward(Tensor zn, Tensor inv_norm, Tensor dzn, Tensor(a!)? dz_bf16, Tensor(b!)? dz_f32) -> ()", &nt_normalize_backward);
   m.def("nt_reduce_loss(Tensor loss_rows, float scale, Tensor(a!) out) -> ()", &nt_reduce_loss);
+  m.def("nt_sup_forward_range(Tensor znT, Tensor ycol, int y0, int R, int col_offset, int n_local, float inv_temp, Tensor(a!) part, int c_lo, int c_hi, int splits, int split_base) -> ()", &nt_sup_forward_range);
+  m.def("nt_sup_finish(Tensor part, int R, int splits, Tensor(a!) lse, Tensor(b!) inv_cnt, Tensor(c!) loss) -> ()", &nt_sup_finish);
+  m.def("nt_sup_backward_part(bool row_mode, Tensor zn, Tensor znT, Tensor lse, Tensor inv_cnt, Tensor ycol, int R, int col_offset, int n_local, float inv_temp, float gscale, Tensor? gout, Tensor(a!) part, int splits, Tensor(b!) out) -> ()", &nt_sup_backward_part);
+  m.def("nt_expand_labels(Tensor labels, Tensor? idx, int views, Tensor(a!) out) -> ()", &nt_expand_labels);
   m.def("lars_norms(Tensor p, Tensor g, Tensor chunk_beg, Tensor chunk_end, float grad_scale, Tensor(a!) norms) -> ()", &lars_norms_op);
   m.def("lars_update(Tensor(a!) p, Tensor g, Tensor(b!) mom, Tensor(c!)? shadow, Tensor chunk_seg, Tensor chunk_beg, Tensor chunk_end, Tensor seg_chunk_beg, Tensor seg_chunk_end, Tensor seg_wd, Tensor seg_flags, Tensor norms, Tensor lr, float momentum, float trust, float eps, float grad_scale, bool nesterov) -> ()", &lars_update_op);
   m.def("lr_step(Tensor(a!) step, Tensor(b!) lr, float lr0, int warmup, int total, int mode) -> ()", &lr_step_op);

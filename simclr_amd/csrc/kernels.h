@@ -225,6 +225,20 @@ void ntxent_backward_part(int row_mode, const float* zn, const float* znT, const
 void ntxent_normalize_backward(const float* zn, const float* inv_norm, const float* dzn, int R,
                                int D, uint16_t* dz_bf16, float* dz_f32, hipStream_t s);
 void ntxent_reduce_loss(const float* loss_rows, int R, float scale, float* out, hipStream_t s);
+// label mode (SupCon): positives = the columns with the anchor's label.  ycol: int32 labels of
+// the columns [y0, ...) (forward) / of every column (backward); part holds 4 floats per row
+void supcon_forward_range(const float* znT, const int* ycol, int y0, int R, int Ccols, int D,
+                          int col_offset, float inv_temp, float* part, int c_lo, int c_hi,
+                          int splits, int split_base, hipStream_t s);
+void supcon_finish(const float* part, int R, int splits, float* lse, float* inv_cnt, float* loss,
+                   hipStream_t s);
+void supcon_backward_part(int row_mode, const float* zn, const float* znT, const float* lse,
+                          const float* inv_cnt, const int* ycol, int R, int Ccols, int D,
+                          int col_offset, float inv_temp, float gscale, const float* gout,
+                          float* part, int splits, float* out, hipStream_t s);
+// out[v*n + i] = labels[idx ? idx[i] : i] (int32 or int64 labels, n_src of them), v < views
+void supcon_expand_labels(const void* labels, int labels_i64, const int64_t* idx, long n_src,
+                          int n, int views, int* out, hipStream_t s);
 
 // ---- lars.hip (flat fp32 master / grad / momentum, bf16 shadow; per-segment table)
 void lars_norms(const float* p, const float* g, const int* chunk_beg, const int* chunk_end,

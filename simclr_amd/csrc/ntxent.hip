@@ -237,6 +237,205 @@ __global__ __launch_bounds__(64) void k_ntxent_bwd(const float* __restrict__ zn,
       dst[(size_t)(o0 + 4 * g + i) * D + dt * 16 + li] = acc[dt][i] * inv_temp;
 }
 
+// ---------------------------------------------------------------- label mode (SupCon)
+// The supervised contrastive loss: the positives of anchor i are every column but its own with
+// the anchor's label, loss_i = LSE_{a≠i} s_ia − (1/|P(i)|) Σ_{p∈P(i)} s_ip.  The kernels below
+// are the NT-Xent ones with the positive test "c == pos_col" replaced by a label compare; they
+// are separate kernels so that the unlabelled ones keep their code.  Labels: ycol[Ccols] int32,
+// one per column (view-expanded, rank-major as the columns).  With all labels distinct the
+// arithmetic is that of NT-Xent operation for operation (one match: the positive sum is that
+// one value plus zeros, the count 1.0f, 1/count 1.0f).
+
+// labels of the four consecutive items [i, i + 4), i % 4 == 0; one 16-byte load if VEC (the
+// host picks VEC = the array is 16-byte aligned; compile-time, so the tile loop stays free of
+// control flow)
+template <bool VEC>
+__device__ __forceinline__ void load_labels4(const int* __restrict__ y, int i, int out[4]) {
+  if (VEC) {
+    const int4 v = *reinterpret_cast<const int4*>(y + i);
+    out[0] = v.x, out[1] = v.y, out[2] = v.z, out[3] = v.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[k] = y[i + k];
+  }
+}
+
+// Forward as k_ntxent_fwd; ycol holds the labels of columns [y0, y0 + len) (the window and the
+// owned rows lie inside).  Writes part[split][r][4] = (max, sumexp, Σ s over matches, count of
+// matches), self excluded.
+template <int D, bool VEC>
+__global__ __launch_bounds__(64) void k_supcon_fwd(const float* __restrict__ znT,
+                                                   const int* __restrict__ ycol, int y0,
+                                                   int R, int Ccols, int col_offset,
+                                                   float inv_temp, int cols_per_split,
+                                                   float* __restrict__ part, int c_lo, int c_hi,
+                                                   int split_base) {
+  const int lane = threadIdx.x;
+  const int g = lane >> 4, li = lane & 15;
+  const int r0 = blockIdx.x * 16;
+  const int split = split_base + blockIdx.y;
+  const int c_beg = c_lo + blockIdx.y * cols_per_split;
+  int c_end = c_beg + cols_per_split;
+  if (c_end > c_hi) c_end = c_hi;
+  float breg[D / 4];
+#pragma unroll
+  for (int ks = 0; ks < D / 4; ++ks)
+    breg[ks] = znT[(size_t)(4 * ks + g) * Ccols + col_offset + r0 + li];
+  const int my_r = r0 + li;  // owned row of this lane (o = li)
+  const int self_c = col_offset + my_r;
+  const int y_own = ycol[self_c - y0];
+  float m = -INFINITY, l = 0.f, psum = 0.f, pcnt = 0.f;
+  for (int q0 = c_beg; q0 < c_end; q0 += 16) {
+    const f32x4_t s = sim_tile<D>(znT, Ccols, q0, breg);
+    int yl[4];
+    load_labels4<VEC>(ycol, q0 + 4 * g - y0, yl);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = q0 + 4 * g + i;
+      const float v = s[i] * inv_temp;
+      if (c != self_c) {
+        if (v > m) {
+          l = l * __expf(m - v) + 1.f;
+          m = v;
+        } else {
+          l += __expf(v - m);
+        }
+        if (yl[i] == y_own) {
+          psum += v;
+          pcnt += 1.f;
+        }
+      }
+    }
+  }
+  // merge across the 4 lane groups (g) holding the same row
+#pragma unroll
+  for (int off = 16; off < 64; off <<= 1) {
+    const float m2 = __shfl_xor(m, off, 64);
+    const float l2 = __shfl_xor(l, off, 64);
+    const float mn = fmaxf(m, m2);
+    l = (mn == -INFINITY) ? 0.f : l * __expf(m - mn) + l2 * __expf(m2 - mn);
+    m = mn;
+    psum += __shfl_xor(psum, off, 64);
+    pcnt += __shfl_xor(pcnt, off, 64);
+  }
+  if (g == 0) {
+    float* dst = part + ((size_t)split * R + my_r) * 4;
+    dst[0] = m;
+    dst[1] = l;
+    dst[2] = psum;
+    dst[3] = pcnt;
+  }
+}
+
+// merge splits in order -> lse[r], inv_cnt[r] = 1/|P(r)|, loss[r]
+__global__ void k_supcon_finish(const float* __restrict__ part, int R, int splits,
+                                float* __restrict__ lse, float* __restrict__ inv_cnt,
+                                float* __restrict__ loss) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  float m = -INFINITY, l = 0.f, ps = 0.f, pc = 0.f;
+  for (int s = 0; s < splits; ++s) {
+    const float* p = part + ((size_t)s * R + r) * 4;
+    const float mn = fmaxf(m, p[0]);
+    if (mn != -INFINITY) l = l * __expf(m - mn) + p[1] * __expf(p[0] - mn);
+    m = mn;
+    ps += p[2];
+    pc += p[3];
+  }
+  const float ls = m + logf(l);
+  const float ic = 1.f / pc;
+  lse[r] = ls;
+  inv_cnt[r] = ic;
+  loss[r] = ls - ps * ic;
+}
+
+// Backward as k_ntxent_bwd with w = gscale·(exp(s−lse_anchor) − [col∈P(anchor)]/|P(anchor)|);
+// ycol covers every column (base 0).
+template <bool ROW, int D, bool VEC>
+__global__ __launch_bounds__(64) void k_supcon_bwd(const float* __restrict__ zn,
+                                                   const float* __restrict__ znT,
+                                                   const float* __restrict__ lse,
+                                                   const float* __restrict__ inv_cnt,
+                                                   const int* __restrict__ ycol, int R,
+                                                   int Ccols, int col_offset, float inv_temp,
+                                                   float gscale, const float* __restrict__ gout,
+                                                   int partners_per_split,
+                                                   float* __restrict__ out) {
+  const int lane = threadIdx.x;
+  const int g = lane >> 4, li = lane & 15;
+  const int o0 = blockIdx.x * 16;  // ROW: local row index; COL: column index
+  const int split = blockIdx.y;
+  const int nown = ROW ? R : Ccols;
+  const int npart = ROW ? Ccols : R;
+  const int q_beg = split * partners_per_split;
+  int q_end = q_beg + partners_per_split;
+  if (q_end > npart) q_end = npart;
+  const float gs = gscale * (gout ? gout[0] : 1.f);
+  const int own_col = ROW ? (col_offset + o0 + li) : (o0 + li);
+  float breg[D / 4];
+#pragma unroll
+  for (int ks = 0; ks < D / 4; ++ks) breg[ks] = znT[(size_t)(4 * ks + g) * Ccols + own_col];
+  const int y_own = ycol[own_col];
+  float lse_own = 0.f, ic_own = 0.f;
+  if (ROW) {
+    lse_own = lse[o0 + li];
+    ic_own = inv_cnt[o0 + li];
+  }
+  constexpr int nd = D / 16;
+  f32x4_t acc[nd];
+#pragma unroll
+  for (int t = 0; t < nd; ++t) acc[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
+  for (int q0 = q_beg; q0 < q_end; q0 += 16) {
+    const int qcol0 = ROW ? q0 : (col_offset + q0);  // partner column index in znT / zn
+    const f32x4_t s = sim_tile<D>(znT, Ccols, qcol0, breg);
+    int yl[4];  // the partners' labels (ROW: columns; COL: anchors, as columns of this rank)
+    load_labels4<VEC>(ycol, qcol0 + 4 * g, yl);
+    float w[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const float v = s[i] * inv_temp;
+      if (ROW) {
+        const int c = q0 + 4 * g + i;
+        const bool self = c == own_col;
+        const float p = self ? 0.f : __expf(v - lse_own);
+        w[i] = gs * (p - ((!self && yl[i] == y_own) ? ic_own : 0.f));
+      } else {
+        const int r = q0 + 4 * g + i;  // anchor (local row)
+        const bool self = own_col == col_offset + r;
+        const float p = self ? 0.f : __expf(v - lse[r]);
+        w[i] = gs * (p - ((!self && yl[i] == y_own) ? inv_cnt[r] : 0.f));
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const float* zrow = zn + (size_t)(qcol0 + 4 * g + t) * D + li;
+#pragma unroll
+      for (int dt = 0; dt < nd; ++dt)
+        acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t], zrow[dt * 16], acc[dt], 0, 0, 0);
+    }
+  }
+  float* dst = out + (size_t)split * nown * D;
+#pragma unroll
+  for (int dt = 0; dt < nd; ++dt)
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      dst[(size_t)(o0 + 4 * g + i) * D + dt * 16 + li] = acc[dt][i] * inv_temp;
+}
+
+// The rank's label block: out[v·n + i] = labels[idx ? idx[i] : i] for every view v, as int32.
+// (idx: the batch's index vector into the dataset's labels; an index outside [0, n_src) is
+// clamped into it, so a bad index cannot read outside the array.)
+template <typename T>
+__global__ void k_expand_labels(const T* __restrict__ labels, const int64_t* __restrict__ idx,
+                                long n_src, int n, int views, int* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  long j = idx ? (long)idx[i] : (long)i;
+  j = j < 0 ? 0 : (j >= n_src ? n_src - 1 : j);
+  const int y = (int)labels[j];
+  for (int v = 0; v < views; ++v) out[(size_t)v * n + i] = y;
+}
+
 // out[r][d] = Σ_s part[s][r][d]   (n elems per split)
 __global__ void k_sum_splits(const float* __restrict__ part, int splits, size_t n,
                              float* __restrict__ out) {
@@ -386,6 +585,85 @@ void ntxent_backward_part(int row_mode, const float* zn, const float* znT, const
   int blocks = (int)((n + 255) / 256);
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(k_sum_splits, dim3(blocks), dim3(256), 0, s, part, splits, n, out);
+  HIP_CHECK_LAUNCH();
+}
+
+// ---- label mode (SupCon)
+static bool labels_vec(const int* y) { return ((uintptr_t)y & 15) == 0; }
+
+void supcon_forward_range(const float* znT, const int* ycol, int y0, int R, int Ccols, int D,
+                          int col_offset, float inv_temp, float* part, int c_lo, int c_hi,
+                          int splits, int split_base, hipStream_t s) {
+  const int ptiles = (c_hi - c_lo) / 16;
+  const int per = ((ptiles + splits - 1) / splits) * 16;
+  const bool yvec = labels_vec(ycol);  // (y0 % 16 == 0: the tile offsets keep the alignment)
+#define FWD_LAUNCH(DD, VV)                                                                    \
+  hipLaunchKernelGGL((k_supcon_fwd<DD, VV>), dim3(R / 16, splits), dim3(64), 0, s, znT, ycol, \
+                     y0, R, Ccols, col_offset, inv_temp, per, part, c_lo, c_hi, split_base)
+#define FWD_CASE(DD)                \
+  case DD:                          \
+    if (yvec) FWD_LAUNCH(DD, true); \
+    else FWD_LAUNCH(DD, false);     \
+    break;
+  switch (D) {
+    FWD_CASE(32) FWD_CASE(64) FWD_CASE(128) FWD_CASE(256)
+    default: fprintf(stderr, "supcon: unsupported D=%d\n", D); abort();
+  }
+#undef FWD_CASE
+#undef FWD_LAUNCH
+  HIP_CHECK_LAUNCH();
+}
+
+void supcon_finish(const float* part, int R, int splits, float* lse, float* inv_cnt, float* loss,
+                   hipStream_t s) {
+  hipLaunchKernelGGL(k_supcon_finish, dim3((R + 255) / 256), dim3(256), 0, s, part, R, splits, lse,
+                     inv_cnt, loss);
+  HIP_CHECK_LAUNCH();
+}
+
+void supcon_backward_part(int row_mode, const float* zn, const float* znT, const float* lse,
+                          const float* inv_cnt, const int* ycol, int R, int Ccols, int D,
+                          int col_offset, float inv_temp, float gscale, const float* gout,
+                          float* part, int splits, float* out, hipStream_t s) {
+  const int nown = row_mode ? R : Ccols;
+  const int npart = row_mode ? Ccols : R;
+  const int ptiles = npart / 16;
+  const int per = ((ptiles + splits - 1) / splits) * 16;
+  const bool yvec = labels_vec(ycol);
+#define BWD_LAUNCH(RR, DD, VV)                                                                 \
+  hipLaunchKernelGGL((k_supcon_bwd<RR, DD, VV>), dim3(nown / 16, splits), dim3(64), 0, s, zn,  \
+                     znT, lse, inv_cnt, ycol, R, Ccols, col_offset, inv_temp, gscale, gout,    \
+                     per, part)
+#define BWD_CASE(DD)                                   \
+  case DD:                                             \
+    if (row_mode && yvec) BWD_LAUNCH(true, DD, true);  \
+    else if (row_mode) BWD_LAUNCH(true, DD, false);    \
+    else if (yvec) BWD_LAUNCH(false, DD, true);        \
+    else BWD_LAUNCH(false, DD, false);                 \
+    break;
+  switch (D) {
+    BWD_CASE(32) BWD_CASE(64) BWD_CASE(128) BWD_CASE(256)
+    default: fprintf(stderr, "supcon: unsupported D=%d\n", D); abort();
+  }
+#undef BWD_CASE
+#undef BWD_LAUNCH
+  HIP_CHECK_LAUNCH();
+  const size_t n = (size_t)nown * D;
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(k_sum_splits, dim3(blocks), dim3(256), 0, s, part, splits, n, out);
+  HIP_CHECK_LAUNCH();
+}
+
+void supcon_expand_labels(const void* labels, int labels_i64, const int64_t* idx, long n_src,
+                          int n, int views, int* out, hipStream_t s) {
+  const dim3 grid((n + 255) / 256), block(256);
+  if (labels_i64)
+    hipLaunchKernelGGL(k_expand_labels<int64_t>, grid, block, 0, s, (const int64_t*)labels, idx,
+                       n_src, n, views, out);
+  else
+    hipLaunchKernelGGL(k_expand_labels<int>, grid, block, 0, s, (const int*)labels, idx, n_src, n,
+                       views, out);
   HIP_CHECK_LAUNCH();
 }
 

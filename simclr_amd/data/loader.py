@@ -108,6 +108,22 @@ class ContrastiveLoader:
         # captured step's static input, so the augmentation writes straight into it (no copy)
         self.with_labels = True
         self.out: Optional[torch.Tensor] = None
+        # ``label_i32`` (SupCon pre-training): the batch's labels as int32, gathered by the
+        # ``nt_expand_labels`` kernel on the GPU — into ``label_out`` in place when that is set
+        # (the captured step's static label buffer, as ``out`` is for the images)
+        self.label_i32 = False
+        self.label_out: Optional[torch.Tensor] = None
+
+    def batch_labels(self, idx: torch.Tensor) -> torch.Tensor:
+        if not self.label_i32:
+            return self.labels[idx]
+        if not self.gpu:
+            return self.labels[idx].to(torch.int32)
+        out = self.label_out
+        if out is None or out.dtype != torch.int32 or tuple(out.shape) != (idx.numel(),):
+            out = torch.empty((idx.numel(),), device=self.device, dtype=torch.int32)
+        torch.ops.simclr_amd.nt_expand_labels(self.labels, idx, 1, out)
+        return out
 
     def set_epoch(self, epoch: int) -> None:
         self.epoch = epoch
@@ -160,7 +176,7 @@ class ContrastiveLoader:
             idx = idx_all[s * self.n:(s + 1) * self.n]
             x = self.batch_from_indices(idx, self.counter)
             self.counter += 1
-            yield x, (self.labels[idx] if self.with_labels else None)
+            yield x, (self.batch_labels(idx) if self.with_labels else None)
 
 
 class EvalLoader:

@@ -16,6 +16,28 @@ Parity default is ``gather=False`` (the reference's loss is per-GPU local).
 
 GPU path: the fused exact-fp32 MFMA kernels of ``csrc/ntxent.hip`` (no N×N logits, no mask or
 concat copies, no host→device target upload per call).  CPU / fp32 path: torch ops.
+
+Extension: the supervised contrastive loss ("SupCon", Khosla et al., L_out^sup without its
+τ/τ_base factor), ``NTXent(..., supervised=True)(z, labels=y)`` or ``SupCon(...)(z, y)``
+(``loss.supervised``).  The contract, identical on the GPU and in :func:`sup_con_torch`:
+
+* Rows are ``z = [view0; view1]``, R = 2n per rank; labels are one integer per image, ``y[n]``;
+  row r has label ``y[r mod n]``.  Labels are compared for equality only (any int32 value).
+* With ``gather=True`` the columns are the all-gathered rows of every rank (Ccols = W·R) and the
+  column labels the all-gathered view-expanded labels, in the same rank-major order.
+* For anchor i (a local row): A(i) = every column except i's own; P(i) = {c ∈ A(i): y_c = y_i}
+  (the other view is always in it, |P(i)| ≥ 1);
+  ``loss_i = LSE_{a∈A(i)} s_ia − (1/|P(i)|) Σ_{p∈P(i)} s_ip`` with ``s = ẑ_i·ẑ_c / τ`` and the
+  NT-Xent normalisation (bf16 z, fp32, eps 1e-12).
+* ``mean`` = Σ_i loss_i / R, ``sum`` the plain sum, ``none`` (2, n) on the torch path only.
+* Gradient in normalised space: ``dS_ia = g·(softmax_ia − [a∈P(i)]/|P(i)|)`` (zero at a = i),
+  contracted by the same row and column passes; the normalisation backward is unchanged.
+* All labels distinct: the loss and dz are bitwise those of NT-Xent on the same device, locally
+  and gathered (the positive sum is a plain fp32 sum in tile, lane-group and split order — one
+  match is that one value —, |P| an exact fp32 count, 1/|P| = 1).
+* Bitwise repeatable: no atomics, a fixed merge order across lane groups and splits.
+* ``gather="ring"`` with ``supervised`` is a ``ValueError``; limits as NT-Xent (R % 16 == 0,
+  D in {32, 64, 128, 256} for the HIP path).
 """
 from __future__ import annotations
 
@@ -49,6 +71,56 @@ def nt_xent_torch(z: torch.Tensor, n: int, temperature: float, reduction: str = 
     sim = sim.masked_fill(self_mask, float("-inf"))
     targets = col_offset + torch.where(idx < n, idx + n, idx - n)
     rows = F.cross_entropy(sim, targets, reduction="none")
+    if reduction == "none":
+        return rows.view(2, n)
+    if reduction == "sum":
+        return rows.sum()
+    return rows.sum() / n * 0.5
+
+
+def _check_labels(labels, n: int, device) -> torch.Tensor:
+    """``labels``: one integer per image, ``y[n]`` (int32 or int64), on z's device."""
+    if not isinstance(labels, torch.Tensor):
+        raise TypeError("labels must be a tensor of n integer class labels")
+    if labels.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"labels must be int32 or int64, not {labels.dtype}")
+    if labels.dim() != 1 or labels.numel() != n:
+        raise ValueError(f"labels must hold one label per image ({n}), got shape "
+                         f"{tuple(labels.shape)}")
+    if labels.device != device:
+        raise ValueError(f"labels must be on z's device ({device}), not {labels.device}")
+    return labels.contiguous()
+
+
+def sup_con_torch(z: torch.Tensor, n: int, labels: torch.Tensor, temperature: float,
+                  reduction: str = "mean", gather: bool = False, group=None,
+                  world_size: int = 1, rank: int = 0):
+    """SupCon oracle on torch ops (the contract in the module docstring); ``z`` = [view0; view1]
+    of shape [2n, d], ``labels`` = y[n].  The same operations as :func:`nt_xent_torch` around
+    the positive term, so that distinct labels give its result bit for bit."""
+    zn = F.normalize(z if z.dtype == torch.float64 else z.float(), p=2, dim=1)
+    R = zn.shape[0]
+    y = _check_labels(labels, n, z.device).to(torch.int64)
+    yrow = torch.cat([y, y])
+    if gather and world_size > 1:
+        from torch.distributed.nn.functional import all_gather
+        cols = torch.cat(all_gather(zn, group=group), dim=0)
+        ys = [torch.empty_like(yrow) for _ in range(world_size)]
+        dist.all_gather(ys, yrow, group=group)
+        ycol = torch.cat(ys)
+        col_offset = rank * R
+    else:
+        cols = zn
+        ycol = yrow
+        col_offset = 0
+    sim = zn @ cols.t() / temperature
+    idx = torch.arange(R, device=z.device)
+    self_mask = torch.zeros_like(sim, dtype=torch.bool)
+    self_mask[idx, col_offset + idx] = True
+    sim = sim.masked_fill(self_mask, float("-inf"))
+    pos = (yrow[:, None] == ycol[None, :]) & ~self_mask  # P(i); the other view is always in it
+    logp = F.log_softmax(sim, dim=1)  # s_ia - LSE_i
+    rows = -(logp.masked_fill(~pos, 0.0).sum(dim=1) / pos.sum(dim=1).to(logp.dtype))
     if reduction == "none":
         return rows.view(2, n)
     if reduction == "sum":
@@ -219,21 +291,167 @@ class _NTXentHipFn(torch.autograd.Function):
         return dz, None, None, None, None, None
 
 
+class _SupConHipFn(torch.autograd.Function):
+    """The label-mode kernels (``nt_sup_*``): the structure of :class:`_NTXentHipFn`, with the
+    rank's view-expanded int32 label block built on the device (``nt_expand_labels``) and, for
+    the gathered loss, all-gathered on the side stream right behind z."""
+
+    @staticmethod
+    def forward(ctx, z, y, n, temperature, reduction, gather, st):
+        from ..ops import _ext
+        ops = _ext.ops()
+        R, D = z.shape
+        dev = z.device
+        zb = z.contiguous() if z.dtype == torch.bfloat16 else z.to(torch.bfloat16).contiguous()
+        inv_t = 1.0 / temperature
+        lse = torch.empty((R,), device=dev, dtype=torch.float32)
+        inv_cnt = torch.empty((R,), device=dev, dtype=torch.float32)
+        rows = torch.empty((R,), device=dev, dtype=torch.float32)
+        y_loc = torch.empty((R,), device=dev, dtype=torch.int32)
+        ops.nt_expand_labels(y, None, 2, y_loc)
+        if gather and st.comm:
+            W = st.world_size
+            col_offset = st.rank * R
+            Ccols = W * R
+            cur = torch.cuda.current_stream(dev)
+            side = _side_stream(dev)
+            side.wait_stream(cur)
+            pre = take_pregather(zb)
+            ipc = getattr(st, "ipc", None)
+            ycol = torch.empty((Ccols,), device=dev, dtype=torch.int32)
+            if pre is not None and tuple(pre[0].shape) == (Ccols, D):
+                zb_all, pre_keep = pre
+            else:
+                pre_keep = pre
+                zb_all = torch.empty((Ccols, D), device=dev, dtype=torch.bfloat16)
+                with torch.cuda.stream(side):
+                    if ipc is not None:
+                        ipc.all_gather(("ntxent", "z"), zb, zb_all)
+                    else:
+                        dist.all_gather_into_tensor(zb_all, zb, group=st.group)
+            with torch.cuda.stream(side):  # the labels: one more small collective, same wait
+                if ipc is not None:
+                    ipc.all_gather(("ntxent", "y"), y_loc, ycol)
+                else:
+                    dist.all_gather_into_tensor(ycol, y_loc, group=st.group)
+            zall = torch.empty((Ccols, D), device=dev, dtype=torch.float32)
+            inv_all = torch.empty((Ccols,), device=dev, dtype=torch.float32)
+            zn = zall[col_offset:col_offset + R]
+            inv = inv_all[col_offset:col_offset + R]
+            znT = torch.empty((D, Ccols), device=dev, dtype=torch.float32)
+            ops.nt_normalize(zb, zn, inv)
+            ops.nt_transpose_cols(zn, znT, col_offset)
+            s_loc = ops.nt_fwd_splits(R, R)
+            s_rem = ops.nt_fwd_splits(R, Ccols - R)
+            part = torch.empty(((s_loc + 2 * s_rem) * R * 4,), device=dev, dtype=torch.float32)
+            # the rank's own block first, with its own labels (overlaps the exchange)
+            ops.nt_sup_forward_range(znT, y_loc, col_offset, R, col_offset, n, inv_t, part,
+                                     col_offset, col_offset + R, s_loc, 0)
+            cur.wait_stream(side)
+            zb_all.record_stream(cur)
+            ycol.record_stream(cur)
+            del pre_keep
+            ops.nt_normalize(zb_all, zall, inv_all)
+            ops.nt_transpose(zall, znT)
+            nsp = s_loc
+            for lo, hi in ((0, col_offset), (col_offset + R, Ccols)):
+                if hi > lo:
+                    sp = max(1, (s_rem * (hi - lo) + (Ccols - R) - 1) // (Ccols - R))
+                    ops.nt_sup_forward_range(znT, ycol, 0, R, col_offset, n, inv_t, part, lo, hi,
+                                             sp, nsp)
+                    nsp += sp
+            ops.nt_sup_finish(part, R, nsp, lse, inv_cnt, rows)
+        else:
+            zn = torch.empty((R, D), device=dev, dtype=torch.float32)
+            inv = torch.empty((R,), device=dev, dtype=torch.float32)
+            ops.nt_normalize(zb, zn, inv)
+            zall = zn
+            ycol = y_loc
+            col_offset = 0
+            Ccols = R
+            znT = torch.empty((D, Ccols), device=dev, dtype=torch.float32)
+            ops.nt_transpose(zall, znT)
+            splits = ops.nt_fwd_splits(R, Ccols)
+            part = torch.empty((splits * R * 4,), device=dev, dtype=torch.float32)
+            ops.nt_sup_forward_range(znT, ycol, 0, R, col_offset, n, inv_t, part, 0, Ccols,
+                                     splits, 0)
+            ops.nt_sup_finish(part, R, splits, lse, inv_cnt, rows)
+        out = torch.empty((1,), device=dev, dtype=torch.float32)
+        scale = 1.0 / R if reduction == "mean" else 1.0
+        ops.nt_reduce_loss(rows, scale, out)
+        ctx.save_for_backward(zn, zall, znT, lse, inv, inv_cnt, ycol)
+        ctx.cfg = (n, inv_t, scale, col_offset, gather, st, z.dtype)
+        return out.view(())
+
+    @staticmethod
+    def backward(ctx, gout):
+        from ..ops import _ext
+        ops = _ext.ops()
+        zn, zall, znT, lse, inv, inv_cnt, ycol = ctx.saved_tensors
+        n, inv_t, scale, col_offset, gather, st, zdtype = ctx.cfg
+        R, D = zn.shape
+        Ccols = zall.shape[0]
+        dev = zn.device
+        g = gout.reshape(1).float().contiguous()
+        s_col = ops.nt_bwd_splits(Ccols, R)
+        part2 = torch.empty((s_col * Ccols * D,), device=dev, dtype=torch.float32)
+        d_cols = torch.empty((Ccols, D), device=dev, dtype=torch.float32)
+        ops.nt_sup_backward_part(False, zall, znT, lse, inv_cnt, ycol, R, col_offset, n, inv_t,
+                                 scale, g, part2, s_col, d_cols)
+        overlap = gather and st.comm and dev.type == "cuda"
+        if overlap:
+            # the column gradient's reduce-scatter, as in NT-Xent (under the row pass)
+            cur = torch.cuda.current_stream(dev)
+            side = _side_stream(dev)
+            side.wait_stream(cur)
+            mine = torch.empty((R, D), device=dev, dtype=torch.float32)
+            with torch.cuda.stream(side):
+                ipc = getattr(st, "ipc", None)
+                if ipc is not None:
+                    ipc.reduce_scatter(("ntxent", "dcols"), d_cols, mine)
+                else:
+                    dist.reduce_scatter_tensor(mine, d_cols, group=st.group)
+        s_row = ops.nt_bwd_splits(R, Ccols)
+        part = torch.empty((s_row * R * D,), device=dev, dtype=torch.float32)
+        d_rows = torch.empty((R, D), device=dev, dtype=torch.float32)
+        ops.nt_sup_backward_part(True, zall, znT, lse, inv_cnt, ycol, R, col_offset, n, inv_t,
+                                 scale, g, part, s_row, d_rows)
+        if overlap:
+            cur.wait_stream(side)
+            d_rows += mine
+        else:
+            d_rows += d_cols[col_offset:col_offset + R]
+        if zdtype == torch.bfloat16:
+            dz = torch.empty((R, D), device=dev, dtype=torch.bfloat16)
+            ops.nt_normalize_backward(zn, inv, d_rows, dz, None)
+        else:
+            dz = torch.empty((R, D), device=dev, dtype=torch.float32)
+            ops.nt_normalize_backward(zn, inv, d_rows, None, dz)
+        return dz, None, None, None, None, None, None
+
+
 class NTXent(nn.Module):
     def __init__(self, temperature: float = 0.1, reduction: str = "mean",
-                 device: Optional[torch.device] = None, gather=False):
+                 device: Optional[torch.device] = None, gather=False, supervised: bool = False):
         """``gather``: False (reference, per-GPU negatives), True (all-gathered global
         negatives, fused kernel) or ``"ring"`` (global negatives circulated around the ranks,
-        loss/ring.py)."""
+        loss/ring.py).  ``supervised``: the SupCon loss (module docstring); ``forward`` then
+        needs ``labels``."""
         assert temperature > 0.0
         assert reduction in {"none", "mean", "sum"}
         super().__init__()
         self.temperature = temperature
         self.reduction = reduction
         self.gather = "ring" if str(gather).lower() == "ring" else bool(gather)
+        self.supervised = bool(supervised)
+        if self.supervised and self.gather == "ring":
+            raise ValueError("loss.supervised=true is not available with loss.gather=ring "
+                             "(use loss.gather=true for global columns)")
 
-    def forward(self, view0: torch.Tensor, view1: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """``forward(view0, view1)`` as the reference, or ``forward(z)`` with z = [view0; view1]."""
+    def forward(self, view0: torch.Tensor, view1: Optional[torch.Tensor] = None,
+                labels: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``forward(view0, view1)`` as the reference, or ``forward(z)`` with z = [view0; view1];
+        ``labels`` = y[n], one integer per image, with ``supervised`` (and only then)."""
         if view1 is not None:
             z = torch.cat([view0, view1], dim=0)
             n = view0.shape[0]
@@ -242,6 +460,19 @@ class NTXent(nn.Module):
             n = z.shape[0] // 2
         st = pstate.get()
         R, D = z.shape
+        if self.supervised:
+            if labels is None:
+                raise ValueError("the supervised loss (loss.supervised) needs labels")
+            y = _check_labels(labels, n, z.device)
+            if (z.is_cuda and self.reduction != "none" and registry.use_hip(z) and R % 16 == 0
+                    and D in (32, 64, 128, 256)):
+                return _SupConHipFn.apply(z, y, n, self.temperature, self.reduction,
+                                          self.gather, st)
+            return sup_con_torch(z, n, y, self.temperature, self.reduction, self.gather,
+                                 st.group, st.world_size, st.rank)
+        if labels is not None:
+            raise ValueError("labels were given but the loss is not supervised "
+                             "(loss.supervised)")
         if self.gather == "ring" and st.comm and st.world_size > 1:
             # global negatives with the column blocks circulating around the ranks (loss/ring.py)
             from .ring import nt_xent_ring
@@ -253,6 +484,17 @@ class NTXent(nn.Module):
             return _NTXentHipFn.apply(z, n, self.temperature, self.reduction, self.gather, st)
         return nt_xent_torch(z, n, self.temperature, self.reduction, self.gather, st.group,
                              st.world_size, st.rank)
+
+
+class SupCon(NTXent):
+    """``NTXent(..., supervised=True)`` with the labels as a positional argument."""
+
+    def __init__(self, temperature: float = 0.1, reduction: str = "mean",
+                 device: Optional[torch.device] = None, gather=False):
+        super().__init__(temperature, reduction, device, gather, supervised=True)
+
+    def forward(self, z: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:  # noqa: D102
+        return super().forward(z, None, labels=labels)
 
 
 # reference class name

@@ -92,8 +92,11 @@ class Trainer:
                              schedule_mode=MODE_WARMUP_COSINE, warmup_steps=self.warmup_steps,
                              total_steps=self.total_steps)
         self._early_updates()
+        # loss.supervised: SupCon (loss/ntxent.py); step() / capture() then need the labels
+        self.supervised = bool(cfg_get(cfg, "loss.supervised", False))
         self.loss_fn = NTXent(temperature=cfg["parameter"]["temperature"],
-                              gather=cfg_get(cfg, "loss.gather", False))
+                              gather=cfg_get(cfg, "loss.gather", False),
+                              supervised=self.supervised)
         # global negatives over RCCL: the fused head gathers z view by view under its GEMM 2
         # (models/head_fused.py _gemm2_pregather)
         zg = self.loss_fn.gather is True and bool(st.comm)
@@ -109,6 +112,7 @@ class Trainer:
         self.replay_mode = "graph"
         self.sreplay = None
         self._static_x = None
+        self._static_y = None  # (supervised: the captured step's labels, filled per batch)
         self._static_loss = None
         self.guard = StepGuard(st)
 
@@ -141,9 +145,26 @@ class Trainer:
             x = x[:, :3]
         return x.contiguous()
 
-    def _step_body(self, x: torch.Tensor) -> torch.Tensor:
+    def _labels(self, x: torch.Tensor, labels: Optional[torch.Tensor]):
+        """The step's labels y[n] on the device (int32 / int64), or None without
+        ``loss.supervised``; a missing or a stray label tensor is an error."""
+        if not self.supervised:
+            if labels is not None:
+                raise ValueError("labels were given but loss.supervised is not set")
+            return None
+        if labels is None:
+            raise ValueError("loss.supervised is set: step() / capture() need the batch's labels")
+        n = x.shape[0] // 2
+        if labels.dim() != 1 or labels.numel() != n:
+            raise ValueError(f"labels must hold one label per image ({n}), got shape "
+                             f"{tuple(labels.shape)}")
+        if labels.dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"labels must be int32 or int64, not {labels.dtype}")
+        return labels.to(self.device)
+
+    def _step_body(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         z = self.model(x, segments=2)
-        loss = self.loss_fn(z)
+        loss = self.loss_fn(z, labels=y) if self.supervised else self.loss_fn(z)
         if not self.hip:
             self.store.zero_grad()
         loss.backward()
@@ -151,14 +172,19 @@ class Trainer:
         self.opt.step()
         return loss.detach()
 
-    def _eager(self, x: torch.Tensor) -> torch.Tensor:
-        return self.guard.run(self._step_body, x)
+    def _eager(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if y is None:
+            return self.guard.run(self._step_body, x)
+        return self.guard.run(self._step_body, x, y)
 
-    def step(self, x: torch.Tensor) -> torch.Tensor:
+    def step(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None) -> torch.Tensor:
         x = self.prepare(x)
+        y = self._labels(x, labels)
         if self.graph is not None:
             if x.data_ptr() != self._static_x.data_ptr():  # (the loader may write in place)
                 self._static_x.copy_(x)
+            if y is not None and y.data_ptr() != self._static_y.data_ptr():
+                self._static_y.copy_(y)  # (the replay reads this batch's labels, never the last)
             if self.replay_mode == "streams" and self.sreplay is not None:
                 self.sreplay.replay()
             else:
@@ -166,20 +192,22 @@ class Trainer:
             self.opt.host_step += 1
             loss = self._static_loss
         else:
-            loss = self._eager(x)
+            loss = self._eager(x, y)
         self.guard.check(self.opt.host_step)
         return loss
 
-    def capture(self, x: torch.Tensor, warmup: int = 2, streams: int = -1) -> None:
+    def capture(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None, warmup: int = 2,
+                streams: int = -1) -> None:
         """Capture one full training step into a hipGraph (after ``warmup`` eager steps) and
         build the native multi-stream executor over its nodes (``streams`` > 0; kept as
         ``self.sreplay``, selected by ``replay_mode = "streams"``)."""
         x = self.prepare(x)
+        y = self._labels(x, labels)
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(s):
             for _ in range(warmup):
-                self._eager(x)
+                self._eager(x, y)
         torch.cuda.current_stream(self.device).wait_stream(s)
         if self.st.comm:
             # the RCCL watchdog polls the end events of the eager warm-up collectives; HIP refuses
@@ -189,6 +217,7 @@ class Trainer:
             torch.cuda.synchronize(self.device)
             time.sleep(1.0)
         self._static_x = x.clone()
+        self._static_y = None if y is None else y.to(torch.int32, copy=True)
         if self.device.type == "cuda":
             from ..ops import _ext
             if _ext.available():
@@ -200,7 +229,7 @@ class Trainer:
         # capture is open: thread-local capture mode keeps those queries legal
         mode = "thread_local" if self.st.comm else "global"
         with torch.cuda.graph(g, capture_error_mode=mode):
-            self._static_loss = self._step_body(self._static_x)
+            self._static_loss = self._step_body(self._static_x, self._static_y)
         self.opt.host_step -= 1  # the captured body incremented it once; replays add per step
         g.instantiate()
         self.graph = g
@@ -260,7 +289,8 @@ def pretrain(cfg) -> dict:
                                world=st.world_size, strength=cfg["experiment"]["strength"],
                                seed=seed, views=2,
                                blur_kernel=blur_kernel_from_cfg(cfg, ds.images.shape[1]))
-    loader.with_labels = False  # SimCLR pre-training uses no labels
+    # SimCLR pre-training uses no labels; loss.supervised (SupCon) keeps them, as int32
+    loader.with_labels = loader.label_i32 = bool(cfg_get(cfg, "loss.supervised", False))
     tr = Trainer(cfg, st, len(ds))
     epochs = cfg["parameter"]["epochs"]
     start_epoch = 1
@@ -288,7 +318,7 @@ def pretrain(cfg) -> dict:
             torch.cuda.synchronize()
         t0 = time.time()
         nsteps = 0
-        for x, _ in loader:
+        for x, y in loader:
             if fault is not None and fault[0] == rank and fault[1] == step_global:
                 log.error("fault injection: rank %d exits with %d at step %d", rank, fault[2],
                           step_global)
@@ -301,7 +331,10 @@ def pretrain(cfg) -> dict:
                 # tuning steps); this batch's step is the captured one, so every batch is
                 # trained exactly once, as in the eager loop
                 try:
-                    tr.capture(x, warmup=0)
+                    if y is not None:
+                        tr.capture(x, y, warmup=0)
+                    else:
+                        tr.capture(x, warmup=0)
                 except Exception as e:
                     if graph_mode == "on":
                         raise
@@ -310,11 +343,12 @@ def pretrain(cfg) -> dict:
                 if tr.graph is not None:
                     tr.replay_mode = str(cfg_get(cfg, "runtime.replay", "streams"))
                     loader.out = tr._static_x  # later batches are augmented in place
+                    loader.label_out = tr._static_y  # (and their labels gathered in place)
                     if rank == 0:
                         log.info("step %d: training step captured; replay mode %s", step_global,
                                  "streams" if (tr.replay_mode == "streams"
                                                and tr.sreplay is not None) else "graph")
-            loss = tr.step(x)
+            loss = tr.step(x, y) if y is not None else tr.step(x)
             nsteps += 1
             step_global += 1
             if log_every and rank == 0 and step_global % log_every == 0:

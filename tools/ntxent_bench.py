@@ -56,5 +56,86 @@ def main():
               flush=True)
 
 
+def _median(v):
+    v = sorted(v)
+    return v[len(v) // 2]
+
+
+def main_supervised(classes, widths, rounds, reps):
+    """``--supervised``: the label-mode (SupCon) kernels against the NT-Xent ones on the same
+    ẑ, alternating the two losses round by round in one process: forward (+finish/reduce),
+    column pass, row pass; medians over the rounds, min-max of the per-round ratio."""
+    from simclr_amd.ops import _ext
+    ops = _ext.ops()
+    dev = torch.device("cuda", 0)
+    R, D, n = 1024, 128, 512
+    for W in widths:
+        C = W * R
+        zall = torch.nn.functional.normalize(torch.randn(C, D, device=dev), dim=1)
+        znT = torch.empty(D, C, device=dev)
+        ops.nt_transpose(zall, znT)
+        splits = ops.nt_fwd_splits(R, C)
+        s_col, s_row = ops.nt_bwd_splits(C, R), ops.nt_bwd_splits(R, C)
+        part3 = torch.empty(splits * R * 3, device=dev)
+        part4 = torch.empty(splits * R * 4, device=dev)
+        lse, rows, icnt = (torch.empty(R, device=dev) for _ in range(3))
+        out, g = torch.empty(1, device=dev), torch.ones(1, device=dev)
+        p2, dc = torch.empty(s_col * C * D, device=dev), torch.empty(C, D, device=dev)
+        p1, dr = torch.empty(s_row * R * D, device=dev), torch.empty(R, D, device=dev)
+        for K in classes:
+            y = torch.randint(0, K, (n,), device=dev, dtype=torch.int32)
+            ycol = torch.empty(C, device=dev, dtype=torch.int32)
+            for w in range(W):  # every rank's block: view-expanded labels of the same classes
+                yw = y if w == 0 else torch.randint(0, K, (n,), device=dev, dtype=torch.int32)
+                ops.nt_expand_labels(yw, None, 2, ycol[w * R:(w + 1) * R])
+
+            def fwd_nt():
+                ops.nt_forward(znT, R, 0, n, 2.0, part3, splits, lse, rows)
+                ops.nt_reduce_loss(rows, 1.0 / R, out)
+
+            def fwd_sup():
+                ops.nt_sup_forward_range(znT, ycol, 0, R, 0, n, 2.0, part4, 0, C, splits, 0)
+                ops.nt_sup_finish(part4, R, splits, lse, icnt, rows)
+                ops.nt_reduce_loss(rows, 1.0 / R, out)
+            arms = {
+                "fwd": (fwd_nt, fwd_sup),
+                "bwd cols": (
+                    lambda: ops.nt_backward_part(False, zall, znT, lse, R, 0, n, 2.0, 1.0 / R, g,
+                                                 p2, s_col, dc),
+                    lambda: ops.nt_sup_backward_part(False, zall, znT, lse, icnt, ycol, R, 0, n,
+                                                     2.0, 1.0 / R, g, p2, s_col, dc)),
+                "bwd rows": (
+                    lambda: ops.nt_backward_part(True, zall, znT, lse, R, 0, n, 2.0, 1.0 / R, g,
+                                                 p1, s_row, dr),
+                    lambda: ops.nt_sup_backward_part(True, zall, znT, lse, icnt, ycol, R, 0, n,
+                                                     2.0, 1.0 / R, g, p1, s_row, dr)),
+            }
+            fwd_sup()  # (lse / inv_cnt of this label set for the backward arms)
+            line = [f"cols={C} classes={K}:"]
+            for name, (f_nt, f_sup) in arms.items():
+                t_nt, t_sup = [], []
+                for _ in range(rounds):
+                    t_nt.append(timeit(f_nt, reps))
+                    t_sup.append(timeit(f_sup, reps))
+                ratios = [b / a for a, b in zip(t_nt, t_sup)]
+                line.append(f"{name} nt-xent {_median(t_nt):.1f} supcon {_median(t_sup):.1f} us "
+                            f"ratio {_median(ratios):.3f} [{min(ratios):.3f}, {max(ratios):.3f}];")
+            print(" ".join(line) + f" splits {splits}/{s_col}/{s_row}", flush=True)
+
+
 if __name__ == "__main__":
-    main()
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("--supervised", action="store_true",
+                    help="time the label-mode (SupCon) kernels against the NT-Xent ones")
+    ap.add_argument("--classes", type=int, nargs="+", default=[10, 100],
+                    help="--supervised: number of distinct labels (one run per value)")
+    ap.add_argument("--ranks", type=int, nargs="+", default=[1, 8],
+                    help="--supervised: column counts as multiples of the 1024 local rows")
+    ap.add_argument("--rounds", type=int, default=15)
+    ap.add_argument("--reps", type=int, default=200)
+    a = ap.parse_args()
+    if a.supervised:
+        main_supervised(a.classes, a.ranks, a.rounds, a.reps)
+    else:
+        main()
