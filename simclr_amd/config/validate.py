@@ -34,10 +34,22 @@ def _check_supervised(cfg) -> None:
            "loss.supervised=true is not available with loss.gather=ring")
 
 
+def _check_online_probe(cfg) -> None:
+    """The opt-in ``online_probe`` group (ops/online_probe.py): a linear classifier trained on
+    the encoder output inside the pre-training step."""
+    from ..ops import online_probe
+    conf = (cfg.get("online_probe") if hasattr(cfg, "get") else None) or {}
+    try:
+        online_probe.validate(conf)
+    except ValueError as err:
+        raise AssertionError(str(err)) from None
+
+
 def check_pretrain_conf(cfg) -> None:
     p, e = cfg["parameter"], cfg["experiment"]
     _check_blur(cfg)
     _check_supervised(cfg)
+    _check_online_probe(cfg)
     _check(p["temperature"] > 0.0, "parameter.temperature must be > 0")
     _check(p["epochs"] > 0, "parameter.epochs must be > 0")
     _check(e["batches"] > 0, "experiment.batches must be > 0")

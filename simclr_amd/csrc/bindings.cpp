@@ -1323,12 +1323,138 @@ void probe_update_op(const Tensor& X, const Tensor& idx, const Tensor& dlT, cons
   probe_update(a, cur_stream());
 }
 
+// ------------------------------------------------------------------------------- online probe
+// shared geometry checks: h [rows][Fp] bf16 (rows = 2n, a multiple of 16), C classes
+struct OnlineProbeGeom {
+  int64_t rows, Rp, Fp, Cp;
+};
+OnlineProbeGeom online_probe_geometry(const char* op, const Tensor& h, int64_t C) {
+  TORCH_CHECK(h.dim() == 2, op, ": h must be [rows][Fp]");
+  OnlineProbeGeom g{h.size(0), (h.size(0) + 31) / 32 * 32, h.size(1), (C + 15) / 16 * 16};
+  TORCH_CHECK(g.rows >= 16 && g.rows % 16 == 0 && g.rows <= online_probe_max_rows(), op,
+              ": rows must be a multiple of 16 in [16, ", online_probe_max_rows(), "], got ",
+              g.rows);
+  TORCH_CHECK(g.Fp >= online_probe_kstep() && g.Fp % online_probe_kstep() == 0 &&
+                  g.Fp <= online_probe_max_fp(),
+              op, ": padded feature width must be a multiple of ", online_probe_kstep(),
+              " and <= ", online_probe_max_fp(), ", got ", g.Fp);
+  TORCH_CHECK(C >= 1 && g.Cp <= online_probe_max_cols(), op, ": C must be in [1, ",
+              online_probe_max_cols(), "], got ", C);
+  return g;
+}
+
+void online_probe_forward_op(const Tensor& h, const Tensor& y, const Tensor& Wsh,
+                             const Tensor& bias, int64_t C, const Tensor& Z, const Tensor& loss,
+                             const Tensor& rank, const Tensor& dlT, const Tensor& dbp) {
+  const char* op = "online_probe_forward";
+  const OnlineProbeGeom g = online_probe_geometry(op, h, C);
+  const int64_t n = y.numel();
+  TORCH_CHECK(n >= 1 && g.rows % n == 0, op, ": y [n] with rows a multiple of n, got rows ",
+              g.rows, " and n ", n);
+  TORCH_CHECK(Wsh.dim() == 2 && Wsh.size(0) == g.Cp && Wsh.size(1) == g.Fp, op, ": Wsh must be [",
+              g.Cp, "][", g.Fp, "]");
+  TORCH_CHECK(bias.numel() == g.Cp, op, ": bias [Cp]");
+  TORCH_CHECK(Z.numel() >= g.rows * g.Cp, op, ": logits scratch [rows][Cp]");
+  TORCH_CHECK(loss.numel() == g.rows && rank.numel() == g.rows, op, ": loss, rank [rows]");
+  TORCH_CHECK(dlT.numel() == g.Cp * g.Rp, op, ": dlT [Cp][rows rounded up to 32]");
+  TORCH_CHECK(dbp.numel() >= g.rows / 16 * g.Cp, op, ": dbp [rows / 16][Cp]");
+  check_dev(rank, at::kInt, "rank");
+  OnlineProbeFwdArgs a{};
+  a.X = bf(h, "h");
+  a.y = i32(y, "y");
+  a.n = (int)n;
+  a.rows = (int)g.rows;
+  a.Rp = (int)g.Rp;
+  a.Fp = (int)g.Fp;
+  a.C = (int)C;
+  a.Cp = (int)g.Cp;
+  a.Wsh = bf(Wsh, "Wsh");
+  a.bias = f32(bias, "bias");
+  a.Z = f32w(Z, "Z");
+  a.loss = f32w(loss, "loss");
+  a.rank = rank.data_ptr<int>();
+  a.dlT = bfw(dlT, "dlT");
+  a.dbp = f32w(dbp, "dbp");
+  online_probe_forward(a, cur_stream());
+}
+
+void online_probe_metrics_op(const Tensor& loss, const Tensor& rank, int64_t top_k,
+                             const Tensor& acc_loss, const Tensor& acc_cnt) {
+  const char* op = "online_probe_metrics";
+  check_dev(rank, at::kInt, "rank");
+  check_dev(acc_loss, at::kDouble, "acc_loss");
+  check_dev(acc_cnt, at::kLong, "acc_cnt");
+  TORCH_CHECK(loss.numel() == rank.numel() && loss.numel() >= 1 &&
+                  loss.numel() <= online_probe_max_rows(),
+              op, ": loss, rank [rows], rows in [1, ", online_probe_max_rows(), "]");
+  TORCH_CHECK(top_k >= 1, op, ": top_k must be >= 1, got ", top_k);
+  TORCH_CHECK(acc_loss.numel() == 1 && acc_cnt.numel() == 3, op, ": acc_loss [1], acc_cnt [3]");
+  online_probe_metrics(f32(loss, "loss"), rank.data_ptr<int>(), (int)loss.numel(),
+                       (int)std::min<int64_t>(top_k, 1 << 30), acc_loss.data_ptr<double>(),
+                       reinterpret_cast<long long*>(acc_cnt.data_ptr<int64_t>()), cur_stream());
+}
+
+void online_probe_wgrad_op(const Tensor& h, const Tensor& dlT, const Tensor& dbp,
+                           const Tensor& grad, int64_t C) {
+  const char* op = "online_probe_wgrad";
+  const OnlineProbeGeom g = online_probe_geometry(op, h, C);
+  TORCH_CHECK(dlT.numel() == g.Cp * g.Rp, op, ": dlT [Cp][rows rounded up to 32]");
+  TORCH_CHECK(dbp.numel() >= g.rows / 16 * g.Cp, op, ": dbp [rows / 16][Cp]");
+  TORCH_CHECK(grad.numel() == g.Cp * g.Fp + g.Cp, op, ": grad [Cp * Fp + Cp]");
+  OnlineProbeGradArgs a{};
+  a.X = bf(h, "h");
+  a.rows = (int)g.rows;
+  a.Rp = (int)g.Rp;
+  a.Fp = (int)g.Fp;
+  a.Cp = (int)g.Cp;
+  a.dlT = bf(dlT, "dlT");
+  a.dbp = f32(dbp, "dbp");
+  a.grad = f32w(grad, "grad");
+  online_probe_wgrad(a, cur_stream());
+}
+
+void online_probe_update_op(const Tensor& master, const Tensor& grad, const Tensor& mom,
+                            const Tensor& shadow, const Tensor& lr, double wd, double momentum,
+                            double gscale, int64_t C, int64_t F, int64_t Fp) {
+  const char* op = "online_probe_update";
+  const int64_t Cp = (C + 15) / 16 * 16;
+  TORCH_CHECK(C >= 1 && Cp <= online_probe_max_cols(), op, ": C must be in [1, ",
+              online_probe_max_cols(), "], got ", C);
+  TORCH_CHECK(Fp >= online_probe_kstep() && Fp % online_probe_kstep() == 0 &&
+                  Fp <= online_probe_max_fp() && F >= 1 && F <= Fp,
+              op, ": F in [1, Fp], Fp a multiple of ", online_probe_kstep(), " and <= ",
+              online_probe_max_fp(), ", got F ", F, " Fp ", Fp);
+  const int64_t total = Cp * Fp + Cp;
+  TORCH_CHECK(master.numel() == total && grad.numel() == total && mom.numel() == total, op,
+              ": master, grad, mom [Cp * Fp + Cp]");
+  TORCH_CHECK(shadow.numel() == Cp * Fp, op, ": shadow [Cp][Fp]");
+  TORCH_CHECK(lr.numel() == 1, op, ": lr [1]");
+  OnlineProbeUpdArgs a{};
+  a.master = f32w(master, "master");
+  a.mom = f32w(mom, "mom");
+  a.grad = f32(grad, "grad");
+  a.shadow = bfw(shadow, "shadow");
+  a.lr = f32(lr, "lr");
+  a.wd = (float)wd;
+  a.momentum = (float)momentum;
+  a.gscale = (float)gscale;
+  a.C = (int)C;
+  a.Cp = (int)Cp;
+  a.F = (int)F;
+  a.Fp = (int)Fp;
+  online_probe_update(a, cur_stream());
+}
+
 }  // namespace
 
 
 TORCH_LIBRARY(simclr_amd, m) {
   m.def("probe_forward(Tensor X, Tensor y, Tensor idx, Tensor Wsh, Tensor bias, int G, int C, Tensor(a!) Z, Tensor(b!) loss, int loss_stride, Tensor(c!)? rank, Tensor(d!)? dlT, Tensor(e!)? dbp) -> ()", &probe_forward_op);
   m.def("probe_update(Tensor X, Tensor idx, Tensor dlT, Tensor dbp, Tensor(a!) W, Tensor(b!) Mw, Tensor(c!) Wsh, Tensor(d!) b, Tensor(e!) Mb, Tensor lr0, Tensor wd, Tensor ftab, int step, float momentum, int G, int C) -> ()", &probe_update_op);
+  m.def("online_probe_forward(Tensor h, Tensor y, Tensor Wsh, Tensor bias, int C, Tensor(a!) Z, Tensor(b!) loss, Tensor(c!) rank, Tensor(d!) dlT, Tensor(e!) dbp) -> ()", &online_probe_forward_op);
+  m.def("online_probe_metrics(Tensor loss, Tensor rank, int top_k, Tensor(a!) acc_loss, Tensor(b!) acc_cnt) -> ()", &online_probe_metrics_op);
+  m.def("online_probe_wgrad(Tensor h, Tensor dlT, Tensor dbp, Tensor(a!) grad, int C) -> ()", &online_probe_wgrad_op);
+  m.def("online_probe_update(Tensor(a!) master, Tensor grad, Tensor(b!) mom, Tensor(c!) shadow, Tensor lr, float wd, float momentum, float gscale, int C, int F, int Fp) -> ()", &online_probe_update_op);
   m.def("knn_normalize(Tensor x, Tensor(a!) out) -> ()", &knn_normalize_op);
   m.def("knn_topk(Tensor qn, Tensor bn, int k, bool exclude_self, int self_offset, Tensor(a!) vals, Tensor(b!) idx) -> ()", &knn_topk_op);
   m.def("knn_scratch_bytes(int Q, int N, int k) -> int", &knn_scratch_bytes_op);

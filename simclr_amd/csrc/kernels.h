@@ -338,3 +338,44 @@ struct ProbeUpdArgs {
   float momentum;
 };
 void probe_update(const ProbeUpdArgs& a, hipStream_t s);
+
+// ---- online_probe.hip: one linear classifier trained on the encoder output inside the captured
+// pre-training step; whatever changes per step is read from device memory
+int online_probe_kstep();     // Fp is F rounded up to this
+int online_probe_max_cols();  // Cp
+int online_probe_max_fp();
+int online_probe_max_rows();
+struct OnlineProbeFwdArgs {
+  const uint16_t* X;    // [rows][Fp] bf16 encoder output, both views
+  const int* y;         // [n] labels: row r has y[r % n]
+  int n, rows, Rp;      // rows % 16 == 0; Rp: rows rounded up to 32
+  int Fp, C, Cp;
+  const uint16_t* Wsh;  // [Cp][Fp] bf16 shadow weights
+  const float* bias;    // [Cp]
+  float* Z;             // [rows][Cp] logits scratch
+  float* loss;          // [rows]
+  int* rank;            // [rows]
+  uint16_t* dlT;        // [Cp][Rp] bf16
+  float* dbp;           // [rows / 16][Cp] bias-gradient partials
+};
+void online_probe_forward(const OnlineProbeFwdArgs& a, hipStream_t s);
+// acc_loss [1] += sum of loss; acc_cnt [3] += (rank == 0, rank < top_k, rows)
+void online_probe_metrics(const float* loss, const int* rank, int rows, int top_k,
+                          double* acc_loss, long long* acc_cnt, hipStream_t s);
+struct OnlineProbeGradArgs {
+  const uint16_t* X;
+  int rows, Rp, Fp, Cp;
+  const uint16_t* dlT;
+  const float* dbp;
+  float* grad;          // [Cp * Fp + Cp]: dW then db
+};
+void online_probe_wgrad(const OnlineProbeGradArgs& a, hipStream_t s);
+struct OnlineProbeUpdArgs {
+  float *master, *mom;  // [Cp * Fp + Cp]
+  const float* grad;
+  uint16_t* shadow;     // [Cp * Fp]
+  const float* lr;      // [1] the probe's LR cell (lr_step)
+  float wd, momentum, gscale;
+  int C, Cp, F, Fp;
+};
+void online_probe_update(const OnlineProbeUpdArgs& a, hipStream_t s);

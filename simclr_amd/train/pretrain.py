@@ -71,7 +71,8 @@ class Trainer:
     eager steps, and the per-step check of the IPC exchange's error flag (``guard.on_error``:
     ``"raise"`` in training, ``"defer"`` in bench.py, which checks collectively)."""
 
-    def __init__(self, cfg, st, dataset_len: int, precision: Optional[str] = None):
+    def __init__(self, cfg, st, dataset_len: int, precision: Optional[str] = None,
+                 num_classes: Optional[int] = None):
         self.cfg = cfg
         self.st = st
         self.device = st.device
@@ -115,6 +116,37 @@ class Trainer:
         self._static_y = None  # (supervised: the captured step's labels, filled per batch)
         self._static_loss = None
         self.guard = StepGuard(st)
+        # online_probe.enabled: a linear classifier trained on the detached encoder output inside
+        # the step (ops/online_probe.py), on a side stream joined before the step ends; built
+        # after the model, so the model's initialisation does not depend on it
+        self.probe = None
+        self._probe_stream = None
+        self._probe_keep = None
+        if bool(cfg_get(cfg, "online_probe.enabled", False)):
+            self.probe = self._build_probe(num_classes)
+
+    def _build_probe(self, num_classes: Optional[int]):
+        from ..ops.online_probe import OnlineProbe, initial_lr
+        cfg, st = self.cfg, self.st
+        if num_classes is None:
+            num_classes = {"cifar10": 10, "cifar100": 100}.get(cfg["experiment"].get("name"))
+        if num_classes is None:
+            raise ValueError("online_probe.enabled needs the dataset's class count "
+                             "(Trainer(num_classes=...))")
+        lin = torch.nn.Linear(self.model.f.num_features, int(num_classes))
+        lr0 = initial_lr(float(cfg_get(cfg, "online_probe.lr", 0.1)),
+                         cfg["experiment"]["batches"], bool(cfg["parameter"]["linear_schedule"]))
+        probe = OnlineProbe(lin.weight, lin.bias, lr0,
+                            decay=float(cfg_get(cfg, "online_probe.decay", 0.0)),
+                            momentum=float(cfg_get(cfg, "online_probe.momentum", 0.9)),
+                            top_k=int(cfg_get(cfg, "online_probe.top_k", 5)),
+                            warmup_steps=self.warmup_steps, total_steps=self.total_steps,
+                            device=self.device, round_operands=self.precision == "bf16",
+                            group=st.group, world_size=st.world_size, comm=bool(st.comm))
+        probe.broadcast_from(0)
+        if self.device.type == "cuda":
+            self._probe_stream = torch.cuda.Stream(device=self.device)
+        return probe
 
     def _early_updates(self) -> None:
         """Single GPU: the fused executor issues the optimizer update of stages 4 (with the
@@ -147,13 +179,16 @@ class Trainer:
 
     def _labels(self, x: torch.Tensor, labels: Optional[torch.Tensor]):
         """The step's labels y[n] on the device (int32 / int64), or None without
-        ``loss.supervised``; a missing or a stray label tensor is an error."""
-        if not self.supervised:
+        ``loss.supervised`` and ``online_probe.enabled``; a missing or a stray label tensor is
+        an error."""
+        if not self.supervised and self.probe is None:
             if labels is not None:
-                raise ValueError("labels were given but loss.supervised is not set")
+                raise ValueError("labels were given but neither loss.supervised nor "
+                                 "online_probe.enabled is set")
             return None
         if labels is None:
-            raise ValueError("loss.supervised is set: step() / capture() need the batch's labels")
+            key = "loss.supervised" if self.supervised else "online_probe.enabled"
+            raise ValueError(f"{key} is set: step() / capture() need the batch's labels")
         n = x.shape[0] // 2
         if labels.dim() != 1 or labels.numel() != n:
             raise ValueError(f"labels must hold one label per image ({n}), got shape "
@@ -163,14 +198,34 @@ class Trainer:
         return labels.to(self.device)
 
     def _step_body(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
-        z = self.model(x, segments=2)
+        if self.probe is None:
+            z = self.model(x, segments=2)
+        else:  # what ContrastiveModel.forward does, with h handed to the probe on the way
+            h = self.model.encode(x, segments=2)
+            self._probe_step(h.detach(), y)
+            z = self.model.g(h, segments=2)
         loss = self.loss_fn(z, labels=y) if self.supervised else self.loss_fn(z)
         if not self.hip:
             self.store.zero_grad()
         loss.backward()
         self.store.finish()
         self.opt.step()
+        if self._probe_keep is not None:  # the step ends only after the probe's launches
+            torch.cuda.current_stream(self.device).wait_stream(self._probe_stream)
+            self._probe_keep = None
         return loss.detach()
+
+    def _probe_step(self, h: torch.Tensor, y: torch.Tensor) -> None:
+        """Forward, metrics, gradient (all-reduced with a data-parallel group) and update of the
+        online probe on its side stream: the launches overlap the head, the loss and the
+        backward, which never read what they write."""
+        if self._probe_stream is None:
+            self.probe.step(h, y)
+            return
+        self._probe_stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self._probe_stream):
+            self.probe.step(h, y)
+        self._probe_keep = h  # (alive until the join: the allocator must not reuse it before)
 
     def _eager(self, x: torch.Tensor, y: Optional[torch.Tensor] = None) -> torch.Tensor:
         if y is None:
@@ -190,6 +245,8 @@ class Trainer:
             else:
                 self.graph.replay()
             self.opt.host_step += 1
+            if self.probe is not None:
+                self.probe.host_step += 1
             loss = self._static_loss
         else:
             loss = self._eager(x, y)
@@ -209,7 +266,9 @@ class Trainer:
             for _ in range(warmup):
                 self._eager(x, y)
         torch.cuda.current_stream(self.device).wait_stream(s)
-        if self.st.comm:
+        # (collectives in the step: the model's, or only the probe's gradient all-reduce)
+        comm = bool(self.st.comm) or (self.probe is not None and self.probe.comm)
+        if comm:
             # the RCCL watchdog polls the end events of the eager warm-up collectives; HIP refuses
             # that query once their stream joins a capture ("event last recorded in a capturing
             # stream").  Let every eager work complete and be reaped (the watchdog polls every
@@ -227,10 +286,12 @@ class Trainer:
         g = torch.cuda.CUDAGraph(keep_graph=True)
         # with collectives in the step, the RCCL watchdog thread polls work events while the
         # capture is open: thread-local capture mode keeps those queries legal
-        mode = "thread_local" if self.st.comm else "global"
+        mode = "thread_local" if comm else "global"
         with torch.cuda.graph(g, capture_error_mode=mode):
             self._static_loss = self._step_body(self._static_x, self._static_y)
         self.opt.host_step -= 1  # the captured body incremented it once; replays add per step
+        if self.probe is not None:
+            self.probe.host_step -= 1
         g.instantiate()
         self.graph = g
         self.sreplay = None
@@ -289,9 +350,11 @@ def pretrain(cfg) -> dict:
                                world=st.world_size, strength=cfg["experiment"]["strength"],
                                seed=seed, views=2,
                                blur_kernel=blur_kernel_from_cfg(cfg, ds.images.shape[1]))
-    # SimCLR pre-training uses no labels; loss.supervised (SupCon) keeps them, as int32
-    loader.with_labels = loader.label_i32 = bool(cfg_get(cfg, "loss.supervised", False))
-    tr = Trainer(cfg, st, len(ds))
+    # SimCLR pre-training uses no labels; loss.supervised (SupCon) and the online probe keep
+    # them, as int32
+    loader.with_labels = loader.label_i32 = bool(
+        cfg_get(cfg, "loss.supervised", False) or cfg_get(cfg, "online_probe.enabled", False))
+    tr = Trainer(cfg, st, len(ds), num_classes=ds.num_classes)
     epochs = cfg["parameter"]["epochs"]
     start_epoch = 1
     resume = cfg_get(cfg, "runtime.resume", None)
@@ -299,6 +362,12 @@ def pretrain(cfg) -> dict:
         blob = load_resume(resume, tr.model, tr.opt, tr.store)
         start_epoch = int(blob["epoch"]) + 1
         loader.counter = int(blob["step"])
+        if tr.probe is not None:
+            if blob.get("online_probe") is not None:
+                tr.probe.load_state_dict(blob["online_probe"])
+            else:
+                log.warning("resume file %s holds no online_probe entry: the online probe "
+                            "starts fresh", resume)
     max_steps = cfg_get(cfg, "runtime.max_steps", None)
     log_every = int(cfg_get(cfg, "runtime.log_every", 0) or 0)  # progress lines (syncs the step)
     graph_mode = _graph_mode(cfg_get(cfg, "runtime.hip_graph", "auto"))
@@ -314,6 +383,8 @@ def pretrain(cfg) -> dict:
     done = False
     for epoch in range(start_epoch, epochs + 1):
         loader.set_epoch(epoch)
+        if tr.probe is not None:
+            tr.probe.reset_metrics()  # (outside the captured step)
         if st.device.type == "cuda":
             torch.cuda.synchronize()
         t0 = time.time()
@@ -371,20 +442,34 @@ def pretrain(cfg) -> dict:
                              where=f"after epoch {epoch}")
         imgs = nsteps * cfg["experiment"]["batches"] * st.world_size
         summary.update(epochs_run=summary["epochs_run"] + 1, steps=step_global)
+        online = {}
+        if tr.probe is not None:
+            # one read of the accumulators (the epoch is synchronised here); collective at W > 1
+            pm = tr.probe.metrics(group=st.group if st.world_size > 1 else None)
+            online = {"online_loss": pm["loss"], "online_acc": pm["acc"],
+                      "online_top_k_acc": pm["top_k_acc"]}
+            summary.update(online, online_rows=pm["rows"])
         if rank == 0:
             lval = float(loss.item())
             lr = tr.opt.logged_lr
             logging.info("Epoch:{}/{} progress:{:.3f} loss:{:.3f}, lr:{:.7f}".format(
                 epoch, epochs, epoch / epochs, lval, lr))
+            if online:  # a second line: the reference's epoch line stays as it is
+                logging.info("Epoch:{}/{} online_loss:{:.3f} online_acc:{:.4f} "
+                             "online_top{}_acc:{:.4f} online_rows:{}".format(
+                                 epoch, epochs, online["online_loss"], online["online_acc"],
+                                 tr.probe.top_k, online["online_top_k_acc"], pm["rows"]))
             metrics.write(epoch=epoch, step=step_global, loss=lval, lr=lr,
-                          images_per_sec=imgs / dt, seconds=dt)
+                          images_per_sec=imgs / dt, seconds=dt, **online)
             summary.update(loss=lval, lr=lr, images_per_sec=imgs / dt)
             if epoch % save_every == 0:
                 save_reference_checkpoint(tr.model, checkpoint_name(
                     epoch, cfg["experiment"]["output_model_name"]))
                 if cfg_get(cfg, "runtime.save_resume", True):
                     save_resume("resume-{}.pt".format(epoch), tr.model, tr.opt, epoch,
-                                loader.counter, group=st.group if st.world_size > 1 else None)
+                                loader.counter, group=st.group if st.world_size > 1 else None,
+                                online_probe=(tr.probe.state_dict() if tr.probe is not None
+                                              else None))
         elif epoch % save_every == 0 and cfg_get(cfg, "runtime.save_resume", True):
             gather_rng_states(dst=0, group=st.group)  # rank 0's resume file holds every rank's
         if st.world_size > 1:

@@ -94,12 +94,16 @@ def gather_rng_states(dst: int = 0, group=None) -> Optional[list]:
 
 
 def save_resume(path: str, model: nn.Module, optimizer, epoch: int, step: int,
-                extra: Optional[dict] = None, group=None) -> None:
+                extra: Optional[dict] = None, group=None,
+                online_probe: Optional[dict] = None) -> None:
     """Resume file (rank 0 writes it).  ``group``: multi-rank job — every other rank must call
     ``gather_rng_states(0, group)`` at the same point, so the file holds each rank's own
-    generators (``rank_rng[r]``), restored per rank by ``restore_rng``."""
+    generators (``rank_rng[r]``), restored per rank by ``restore_rng``.  ``online_probe``: the
+    online probe's ``state_dict()`` (master, momentum, step), stored under that key; without
+    it the file has no such entry."""
     local = _local_rng()
     ranks = gather_rng_states(0, group) if group is not None else [local]
+    probe = {} if online_probe is None else {"online_probe": online_probe}
     torch.save({
         "model": reference_state_dict(model),
         "optimizer": optimizer.state_dict() if optimizer is not None else None,
@@ -109,6 +113,7 @@ def save_resume(path: str, model: nn.Module, optimizer, epoch: int, step: int,
         "numpy_rng": local["numpy_rng"],
         "rank_rng": ranks,
         "extra": extra or {},
+        **probe,
     }, path)
 
 
