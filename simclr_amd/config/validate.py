@@ -34,6 +34,28 @@ def _check_supervised(cfg) -> None:
            "loss.supervised=true is not available with loss.gather=ring")
 
 
+LOSS_KINDS = ("ntxent", "barlow")
+
+
+def _check_loss_kind(cfg) -> None:
+    """The opt-in ``loss.kind`` (``ntxent`` | ``barlow``, loss/barlow.py) and
+    ``loss.barlow_lambda``; Barlow Twins is per rank and has no labels."""
+    loss = (cfg.get("loss") if hasattr(cfg, "get") else None) or {}
+    kind = loss.get("kind")
+    _check(kind is None or (isinstance(kind, str) and kind in LOSS_KINDS),
+           f"loss.kind must be one of {', '.join(LOSS_KINDS)}")
+    lam = loss.get("barlow_lambda")
+    if lam is not None:
+        _check(isinstance(lam, (int, float)) and not isinstance(lam, bool),
+               "loss.barlow_lambda must be a number")
+        _check(lam > 0.0, "loss.barlow_lambda must be > 0")
+    if kind == "barlow":
+        _check(not loss.get("supervised"),
+               "loss.kind=barlow is not available with loss.supervised=true")
+        _check(loss.get("gather") in (None, False),
+               "loss.kind=barlow is not available with loss.gather (the loss is per rank)")
+
+
 def _check_online_probe(cfg) -> None:
     """The opt-in ``online_probe`` group (ops/online_probe.py): a linear classifier trained on
     the encoder output inside the pre-training step."""
@@ -49,6 +71,7 @@ def check_pretrain_conf(cfg) -> None:
     p, e = cfg["parameter"], cfg["experiment"]
     _check_blur(cfg)
     _check_supervised(cfg)
+    _check_loss_kind(cfg)
     _check_online_probe(cfg)
     _check(p["temperature"] > 0.0, "parameter.temperature must be > 0")
     _check(p["epochs"] > 0, "parameter.epochs must be > 0")

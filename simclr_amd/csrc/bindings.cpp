@@ -935,6 +935,89 @@ void nt_expand_labels(const Tensor& labels, const c10::optional<Tensor>& idx, in
                        (int)views, out.data_ptr<int>(), cur_stream());
 }
 
+// ------------------------------------------------------------------------------- barlow twins
+// (csrc/barlow.hip; every tensor's size is checked against n and D before any launch)
+void check_bt(int64_t n, int64_t D) {
+  TORCH_CHECK(n >= 32 && n % 32 == 0 && n <= (1 << 20), "barlow: n must be a multiple of 32 in "
+              "[32, 2^20], got ", n);
+  TORCH_CHECK(D >= 64 && D <= 2048 && D % 64 == 0, "barlow: D must be a multiple of 64 in "
+              "[64, 2048], got ", D);
+}
+void bt_standardize(const Tensor& z, double eps, const Tensor& rstd, const Tensor& zh,
+                    const Tensor& zhT) {
+  TORCH_CHECK(z.dim() == 2 && z.size(0) % 2 == 0, "bt_standardize: z must be [2n][D]");
+  const int64_t n = z.size(0) / 2, D = z.size(1);
+  check_bt(n, D);
+  TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
+                  (z.scalar_type() == at::kBFloat16 || z.scalar_type() == at::kFloat),
+              "bt_standardize: z must be a contiguous bf16 or fp32 GPU tensor");
+  TORCH_CHECK(eps > 0.0, "bt_standardize: eps must be > 0");
+  TORCH_CHECK(rstd.numel() == 2 * D && zh.numel() == 2 * n * D && zhT.numel() == 2 * n * D,
+              "bt_standardize sizes");
+  barlow_standardize(z.data_ptr(), z.scalar_type() == at::kFloat ? 1 : 0, (int)n, (int)D,
+                     (float)eps, f32w(rstd, "rstd"), bfw(zh, "zh"), bfw(zhT, "zhT"), cur_stream());
+}
+int64_t bt_corr_splits(int64_t n, int64_t D) {
+  check_bt(n, D);
+  return barlow_corr_splits((int)n, (int)D);
+}
+int64_t bt_loss_blocks(int64_t D) {
+  check_bt(32, D);
+  return barlow_loss_blocks((int)D);
+}
+void bt_corr(const Tensor& zhT, int64_t n, int64_t splits, const Tensor& part) {
+  TORCH_CHECK(zhT.dim() == 3 && zhT.size(0) == 2 && zhT.size(2) == n, "bt_corr: zhT is [2][D][n]");
+  const int64_t D = zhT.size(1);
+  check_bt(n, D);
+  TORCH_CHECK(splits >= 1 && splits <= n / 32 && part.numel() == splits * D * D,
+              "bt_corr: part must be [splits][D][D] with 1 <= splits <= n / 32");
+  barlow_corr(bf(zhT, "zhT"), (int)n, (int)D, (int)splits, f32w(part, "part"), cur_stream());
+}
+void bt_loss(const Tensor& part, int64_t splits, int64_t n, double lambd, const Tensor& C,
+             const Tensor& lpart) {
+  TORCH_CHECK(C.dim() == 2 && C.size(0) == C.size(1), "bt_loss: C is [D][D]");
+  const int64_t D = C.size(0);
+  check_bt(n, D);
+  TORCH_CHECK(splits >= 1 && part.numel() == splits * D * D &&
+                  lpart.numel() == barlow_loss_blocks((int)D), "bt_loss sizes");
+  barlow_loss(f32(part, "part"), (int)splits, (int)n, (int)D, (float)lambd, f32w(C, "C"),
+              f32w(lpart, "lpart"), cur_stream());
+}
+void bt_grad(const Tensor& C, double lambd, const Tensor& gout, const Tensor& G,
+             const Tensor& GT) {
+  TORCH_CHECK(C.dim() == 2 && C.size(0) == C.size(1), "bt_grad: C is [D][D]");
+  const int64_t D = C.size(0);
+  check_bt(32, D);
+  TORCH_CHECK(gout.numel() == 1 && G.numel() == D * D && GT.numel() == D * D, "bt_grad sizes");
+  barlow_grad(f32(C, "C"), (int)D, (float)lambd, f32(gout, "gout"), bfw(G, "G"), bfw(GT, "GT"),
+              cur_stream());
+}
+void bt_backward(const Tensor& zh, const Tensor& G, const Tensor& GT, const Tensor& dzh,
+                 const Tensor& colpart) {
+  TORCH_CHECK(zh.dim() == 2 && zh.size(0) % 2 == 0, "bt_backward: zh must be [2n][D]");
+  const int64_t n = zh.size(0) / 2, D = zh.size(1);
+  check_bt(n, D);
+  TORCH_CHECK(G.numel() == D * D && GT.numel() == D * D && dzh.numel() == 2 * n * D &&
+                  colpart.numel() == 2 * (n / 32) * 2 * D, "bt_backward sizes");
+  barlow_backward(bf(zh, "zh"), bf(G, "G"), bf(GT, "GT"), (int)n, (int)D, f32w(dzh, "dzh"),
+                  f32w(colpart, "colpart"), cur_stream());
+}
+void bt_std_backward(const Tensor& zh, const Tensor& rstd, const Tensor& dzh,
+                     const Tensor& colpart, const c10::optional<Tensor>& dz_bf16,
+                     const c10::optional<Tensor>& dz_f32) {
+  TORCH_CHECK(zh.dim() == 2 && zh.size(0) % 2 == 0, "bt_std_backward: zh must be [2n][D]");
+  const int64_t n = zh.size(0) / 2, D = zh.size(1);
+  check_bt(n, D);
+  TORCH_CHECK(rstd.numel() == 2 * D && dzh.numel() == 2 * n * D &&
+                  colpart.numel() == 2 * (n / 32) * 2 * D, "bt_std_backward sizes");
+  uint16_t* ob = optbfw(dz_bf16, "dz_bf16");
+  float* of = optf32w(dz_f32, "dz_f32");
+  TORCH_CHECK((ob != nullptr) != (of != nullptr), "bt_std_backward: one of dz_bf16 / dz_f32");
+  TORCH_CHECK((ob ? dz_bf16->numel() : dz_f32->numel()) == 2 * n * D, "bt_std_backward: dz size");
+  barlow_std_backward(bf(zh, "zh"), f32(rstd, "rstd"), f32(dzh, "dzh"), f32(colpart, "colpart"),
+                      (int)n, (int)D, ob, of, cur_stream());
+}
+
 // ------------------------------------------------------------------------------- lars
 void lars_norms_op(const Tensor& p, const Tensor& g, const Tensor& chunk_beg,
                    const Tensor& chunk_end, double grad_scale, const Tensor& norms) {
@@ -1536,6 +1619,14 @@ TORCH_LIBRARY(simclr_amd, m) {
   m.def("nt_sup_finish(Tensor part, int R, int splits, Tensor(a!) lse, Tensor(b!) inv_cnt, Tensor(c!) loss) -> ()", &nt_sup_finish);
   m.def("nt_sup_backward_part(bool row_mode, Tensor zn, Tensor znT, Tensor lse, Tensor inv_cnt, Tensor ycol, int R, int col_offset, int n_local, float inv_temp, float gscale, Tensor? gout, Tensor(a!) part, int splits, Tensor(b!) out) -> ()", &nt_sup_backward_part);
   m.def("nt_expand_labels(Tensor labels, Tensor? idx, int views, Tensor(a!) out) -> ()", &nt_expand_labels);
+  m.def("bt_standardize(Tensor z, float eps, Tensor(a!) rstd, Tensor(b!) zh, Tensor(c!) zhT) -> ()", &bt_standardize);
+  m.def("bt_corr_splits(int n, int D) -> int", &bt_corr_splits);
+  m.def("bt_loss_blocks(int D) -> int", &bt_loss_blocks);
+  m.def("bt_corr(Tensor zhT, int n, int splits, Tensor(a!) part) -> ()", &bt_corr);
+  m.def("bt_loss(Tensor part, int splits, int n, float lambd, Tensor(a!) C, Tensor(b!) lpart) -> ()", &bt_loss);
+  m.def("bt_grad(Tensor C, float lambd, Tensor gout, Tensor(a!) G, Tensor(b!) GT) -> ()", &bt_grad);
+  m.def("bt_backward(Tensor zh, Tensor G, Tensor GT, Tensor(a!) dzh, Tensor(b!) colpart) -> ()", &bt_backward);
+  m.def("bt_std_backward(Tensor zh, Tensor rstd, Tensor dzh, Tensor colpart, Tensor(a!)? dz_bf16, Tensor(b!)? dz_f32) -> ()", &bt_std_backward);
   m.def("lars_norms(Tensor p, Tensor g, Tensor chunk_beg, Tensor chunk_end, float grad_scale, Tensor(a!) norms) -> ()", &lars_norms_op);
   m.def("lars_update(Tensor(a!) p, Tensor g, Tensor(b!) mom, Tensor(c!)? shadow, Tensor chunk_seg, Tensor chunk_beg, Tensor chunk_end, Tensor seg_chunk_beg, Tensor seg_chunk_end, Tensor seg_wd, Tensor seg_flags, Tensor norms, Tensor lr, float momentum, float trust, float eps, float grad_scale, bool nesterov) -> ()", &lars_update_op);
   m.def("lr_step(Tensor(a!) step, Tensor(b!) lr, float lr0, int warmup, int total, int mode) -> ()", &lr_step_op);

@@ -240,6 +240,28 @@ void supcon_backward_part(int row_mode, const float* zn, const float* znT, const
 void supcon_expand_labels(const void* labels, int labels_i64, const int64_t* idx, long n_src,
                           int n, int views, int* out, hipStream_t s);
 
+// ---- barlow.hip  (Barlow Twins: cross-correlation over the batch on v_mfma_f32_16x16x32_bf16)
+// n % 32 == 0, D % 64 == 0, 64 <= D <= 2048.  z [2n][D] (bf16, or fp32 with z_f32) ->
+// rstd [2][D], zh bf16 [2n][D], zhT bf16 [2][D][n]
+void barlow_standardize(const void* z, int z_f32, int n, int D, float eps, float* rstd,
+                        uint16_t* zh, uint16_t* zhT, hipStream_t s);
+int barlow_corr_splits(int n, int D);
+// part [splits][D][D]: the correlation over slices of the batch (unscaled)
+void barlow_corr(const uint16_t* zhT, int n, int D, int splits, float* part, hipStream_t s);
+int barlow_loss_blocks(int D);
+// C [D][D] = (Σ part) / n, lpart[barlow_loss_blocks(D)] = partial sums of the loss terms
+void barlow_loss(const float* part, int splits, int n, int D, float lambd, float* C, float* lpart,
+                 hipStream_t s);
+// G, GT bf16 [D][D] from C and the upstream scalar gout[0]
+void barlow_grad(const float* C, int D, float lambd, const float* gout, uint16_t* G, uint16_t* GT,
+                 hipStream_t s);
+// dzh fp32 [2n][D], colpart [2][n/32][2][D] (per row tile: column sums of dzh and of dzh·zh)
+void barlow_backward(const uint16_t* zh, const uint16_t* G, const uint16_t* GT, int n, int D,
+                     float* dzh, float* colpart, hipStream_t s);
+void barlow_std_backward(const uint16_t* zh, const float* rstd, const float* dzh,
+                         const float* colpart, int n, int D, uint16_t* dz_bf16, float* dz_f32,
+                         hipStream_t s);
+
 // ---- lars.hip (flat fp32 master / grad / momentum, bf16 shadow; per-segment table)
 void lars_norms(const float* p, const float* g, const int* chunk_beg, const int* chunk_end,
                 int nchunks, float grad_scale, float* norms, hipStream_t s);

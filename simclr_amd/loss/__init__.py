@@ -1,0 +1,1 @@
+from .barlow import BarlowTwins, barlow_twins_torch  # noqa: F401

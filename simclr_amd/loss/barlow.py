@@ -1,0 +1,215 @@
+"""Barlow Twins loss (Zbontar et al., 2021): redundancy reduction on the D x D cross-correlation
+of the two views' embeddings.  No negatives and no temperature, so the loss does not depend on
+the batch size the way NT-Xent does (``loss.kind=barlow``).
+
+The contract, identical in the kernels of ``csrc/barlow.hip`` and in :func:`barlow_twins_torch`:
+
+* Rows are ``z = [view0; view1]``, ``[2n][D]``.  On the HIP path z is the head's bf16 output; an
+  fp32 z is read as given.  dz comes back in z's dtype.
+* Standardisation per view v and column d, in fp32 and a fixed row order:
+  ``μ = (1/n) Σ_b z``, then ``σ² = (1/n) Σ_b (z − μ)²`` (biased, two passes),
+  ``ẑ = (z − μ) · rsqrt(σ² + eps)`` — the paper's ``BatchNorm1d(affine=False)``.  The row order
+  is :func:`_row_sum`'s in the kernel and in the twin, and rsqrt is the correctly rounded
+  ``1 / sqrt``, so both round the same ẑ to bf16.  A constant
+  column gives ẑ = 0, never NaN.  With ``round_operands`` (the HIP path always) ẑ is rounded once
+  to bf16; everything below is exact on those operands up to the fp32 summation order.
+* ``C = ẑ0ᵀ ẑ1 / n`` (fp32 accumulation over the whole batch; the kernels split the batch over
+  blocks and merge the partial slabs in split order, no atomics).
+* ``loss = Σ_i (1 − C_ii)² + λ Σ_{i≠j} C_ij²``, a fixed-order fp32 sum.  No reduction modes.
+* Backward, g the upstream scalar: ``G_ii = −2g(1 − C_ii)``, ``G_ij = 2gλ C_ij``, rounded once to
+  bf16 with ``round_operands`` (it is the operand of the next GEMMs); ``dẑ0 = ẑ1 · Gᵀ / n``,
+  ``dẑ1 = ẑ0 · G / n`` (fp32 accumulation, K = D); per view and column, on the ẑ the forward kept,
+  ``dz = rsqrt(σ²+eps) · (dẑ − mean_b(dẑ) − ẑ · mean_b(dẑ·ẑ))`` with fp32 means.
+* Bitwise repeatable.  No host value that changes per step reaches a launch (g is read on the
+  device), and the allocations are ``torch.empty`` calls as in ``_NTXentHipFn``, so a step with
+  this loss captures as one with NT-Xent does.
+* HIP path: ``n % 32 == 0``, ``D % 64 == 0``, ``64 <= D <= 2048`` and ``registry.use_hip(z)``;
+  anything else takes the twin (unrounded, in fp32; fp64 for a ``double`` z).
+* Data-parallel runs: the loss is per rank (each rank correlates its own n images) and the
+  gradients are averaged by the flat store's buckets; an all-reduced C is not implemented.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import torch
+from torch import nn
+
+from ..ops import registry
+
+
+def _bf16_round(x: torch.Tensor) -> torch.Tensor:
+    return x.to(torch.bfloat16).to(x.dtype)
+
+
+ROW_GROUPS = 16  # of the fixed row order (k_bt_standardize's 16 row groups)
+
+
+def _row_sum(x: torch.Tensor) -> torch.Tensor:
+    """x [2][n][D] -> [2][1][D], the rows added in the contract's fixed order: group r of 16 adds
+    rows r, r + 16, r + 32, ... in order, then the 16 groups are added in order (the order of
+    ``k_bt_standardize``, so the statistics have the same bits on every device).  n that is no
+    multiple of 16 (never the kernels' case) takes ``sum``."""
+    v, n, D = x.shape
+    if n % ROW_GROUPS:
+        return x.sum(dim=1, keepdim=True)
+    xg = x.view(v, n // ROW_GROUPS, ROW_GROUPS, D)
+    acc = xg[:, 0]
+    for k in range(1, n // ROW_GROUPS):
+        acc = acc + xg[:, k]
+    tot = acc[:, 0]
+    for k in range(1, ROW_GROUPS):
+        tot = tot + acc[:, k]
+    return tot.unsqueeze(1)
+
+
+def _standardize(zf: torch.Tensor, n: int, eps: float):
+    """zf [2n][D] -> ẑ [2][n][D], rstd [2][1][D] (biased, two passes; rsqrt as the correctly
+    rounded 1 / sqrt)."""
+    zv = zf.view(2, n, zf.shape[1])
+    dt = zf.dtype
+    # quotients and the root through fp64, rounded once to z's precision: correctly rounded on
+    # every device (torch's fp32 division and sqrt on the GPU are not), as in k_bt_standardize
+    mu = (_row_sum(zv).double() / n).to(dt)
+    c = zv - mu
+    var = (_row_sum(c * c).double() / n).to(dt)
+    rstd = (1.0 / torch.sqrt((var + eps).double()).to(dt).double()).to(dt)
+    return c * rstd, rstd
+
+
+def _loss_terms(C: torch.Tensor, lambd: float) -> torch.Tensor:
+    eye = torch.eye(C.shape[0], dtype=torch.bool, device=C.device)
+    om = 1.0 - C
+    return torch.where(eye, om * om, (lambd * C) * C).sum()
+
+
+class _BarlowTwinFn(torch.autograd.Function):
+    """The twin with ``round_operands``: ẑ and G rounded to bf16 at the kernels' points."""
+
+    @staticmethod
+    def forward(ctx, z, n, lambd, eps):
+        zh, rstd = _standardize(z.float(), n, eps)
+        zh = _bf16_round(zh)
+        C = zh[0].t() @ zh[1] / n
+        ctx.save_for_backward(zh, rstd, C)
+        ctx.cfg = (n, lambd, z.dtype)
+        ctx.mark_non_differentiable(C)
+        return _loss_terms(C, lambd), C
+
+    @staticmethod
+    def backward(ctx, gout, _gc):
+        zh, rstd, C = ctx.saved_tensors
+        n, lambd, zdtype = ctx.cfg
+        g = gout.float()
+        eye = torch.eye(C.shape[0], dtype=torch.bool, device=C.device)
+        G = _bf16_round(torch.where(eye, (-2.0 * g) * (1.0 - C), (2.0 * g * lambd) * C))
+        dzh = torch.stack([zh[1] @ G.t(), zh[0] @ G]) / n
+        m1 = dzh.sum(dim=1, keepdim=True) / n
+        m2 = (dzh * zh).sum(dim=1, keepdim=True) / n
+        dz = rstd * ((dzh - m1) - zh * m2)
+        return dz.reshape(2 * n, -1).to(zdtype), None, None, None
+
+
+def barlow_twins_torch(z: torch.Tensor, n: int, lambd: float, eps: float = 1e-5,
+                       round_operands: bool = False, return_c: bool = False):
+    """The loss on torch ops; ``z`` = [view0; view1] of shape [2n, D].  Without
+    ``round_operands`` these are plain differentiable ops (a ``double`` z gives the fp64 oracle);
+    with it, an explicit function that rounds ẑ and G to bf16 where the kernels do.
+    ``return_c``: also return C (not differentiable with ``round_operands``)."""
+    if z.dim() != 2 or z.shape[0] != 2 * n:
+        raise ValueError(f"z must be [2n][D] with n = {n}, got {tuple(z.shape)}")
+    if round_operands:
+        loss, C = _BarlowTwinFn.apply(z, n, float(lambd), float(eps))
+    else:
+        zh, _ = _standardize(z if z.dtype == torch.float64 else z.float(), n, eps)
+        C = zh[0].t() @ zh[1] / n
+        loss = _loss_terms(C, float(lambd))
+    return (loss, C) if return_c else loss
+
+
+class _BarlowHipFn(torch.autograd.Function):
+    """Seven launches: standardise, correlate, loss partials, their sum; G, dẑ, dz."""
+
+    @staticmethod
+    def forward(ctx, z, n, lambd, eps):
+        from ..ops import _ext
+        ops = _ext.ops()
+        D = z.shape[1]
+        dev = z.device
+        zc = z.contiguous()
+        rstd = torch.empty((2, D), device=dev, dtype=torch.float32)
+        zh = torch.empty((2 * n, D), device=dev, dtype=torch.bfloat16)
+        zhT = torch.empty((2, D, n), device=dev, dtype=torch.bfloat16)
+        ops.bt_standardize(zc, eps, rstd, zh, zhT)
+        splits = ops.bt_corr_splits(n, D)
+        part = torch.empty((splits, D, D), device=dev, dtype=torch.float32)
+        ops.bt_corr(zhT, n, splits, part)
+        C = torch.empty((D, D), device=dev, dtype=torch.float32)
+        lpart = torch.empty((ops.bt_loss_blocks(D),), device=dev, dtype=torch.float32)
+        ops.bt_loss(part, splits, n, lambd, C, lpart)
+        out = torch.empty((1,), device=dev, dtype=torch.float32)
+        ops.nt_reduce_loss(lpart, 1.0, out)
+        ctx.save_for_backward(zh, rstd, C)
+        ctx.cfg = (n, lambd, z.dtype)
+        ctx.mark_non_differentiable(C)
+        return out.view(()), C
+
+    @staticmethod
+    def backward(ctx, gout, _gc):
+        from ..ops import _ext
+        ops = _ext.ops()
+        zh, rstd, C = ctx.saved_tensors
+        n, lambd, zdtype = ctx.cfg
+        D = zh.shape[1]
+        dev = zh.device
+        g = gout.reshape(1).float().contiguous()
+        G = torch.empty((D, D), device=dev, dtype=torch.bfloat16)
+        GT = torch.empty((D, D), device=dev, dtype=torch.bfloat16)
+        ops.bt_grad(C, lambd, g, G, GT)
+        dzh = torch.empty((2 * n, D), device=dev, dtype=torch.float32)
+        colpart = torch.empty((2, n // 32, 2, D), device=dev, dtype=torch.float32)
+        ops.bt_backward(zh, G, GT, dzh, colpart)
+        if zdtype == torch.bfloat16:
+            dz = torch.empty((2 * n, D), device=dev, dtype=torch.bfloat16)
+            ops.bt_std_backward(zh, rstd, dzh, colpart, dz, None)
+        else:
+            dz = torch.empty((2 * n, D), device=dev, dtype=torch.float32)
+            ops.bt_std_backward(zh, rstd, dzh, colpart, None, dz)
+        return dz, None, None, None
+
+
+def hip_path(z: torch.Tensor, n: int) -> bool:
+    """Whether ``z`` = [2n][D] takes the kernels (the limits in the module docstring)."""
+    D = z.shape[1]
+    return (z.is_cuda and z.dtype in (torch.bfloat16, torch.float32) and n >= 32 and n % 32 == 0
+            and D % 64 == 0 and 64 <= D <= 2048 and registry.use_hip(z))
+
+
+class BarlowTwins(nn.Module):
+    def __init__(self, lambd: float = 0.0051, eps: float = 1e-5):
+        """``lambd``: the weight of the off-diagonal (redundancy) term, the paper's 0.0051;
+        ``eps``: the standardisation's, BatchNorm1d's 1e-5."""
+        if not lambd > 0.0:
+            raise ValueError(f"loss.barlow_lambda must be > 0, got {lambd}")
+        if not eps > 0.0:
+            raise ValueError(f"eps must be > 0, got {eps}")
+        super().__init__()
+        self.lambd = float(lambd)
+        self.eps = float(eps)
+
+    def forward(self, view0: torch.Tensor, view1: Optional[torch.Tensor] = None,
+                return_c: bool = False):
+        """``forward(view0, view1)`` or ``forward(z)`` with z = [view0; view1], as ``NTXent``;
+        returns the scalar loss (``return_c``: and C, for inspection)."""
+        if view1 is not None:
+            z = torch.cat([view0, view1], dim=0)
+            n = view0.shape[0]
+        else:
+            z = view0
+            n = z.shape[0] // 2
+        if z.dim() != 2 or z.shape[0] != 2 * n:
+            raise ValueError(f"z must be [2n][D], got {tuple(z.shape)}")
+        if hip_path(z, n):
+            loss, C = _BarlowHipFn.apply(z, n, self.lambd, self.eps)
+            return (loss, C) if return_c else loss
+        return barlow_twins_torch(z, n, self.lambd, self.eps, return_c=return_c)

@@ -36,6 +36,7 @@ from ..comm.ipc import StepGuard
 from ..config import check_pretrain_conf
 from ..data.datasets import load_dataset
 from ..data.loader import ContrastiveLoader, blur_kernel_from_cfg
+from ..loss.barlow import BarlowTwins
 from ..loss.ntxent import NTXent
 from ..models.contrastive import ContrastiveModel
 from ..ops import registry
@@ -95,12 +96,22 @@ class Trainer:
         self._early_updates()
         # loss.supervised: SupCon (loss/ntxent.py); step() / capture() then need the labels
         self.supervised = bool(cfg_get(cfg, "loss.supervised", False))
-        self.loss_fn = NTXent(temperature=cfg["parameter"]["temperature"],
-                              gather=cfg_get(cfg, "loss.gather", False),
-                              supervised=self.supervised)
+        # loss.kind: ntxent (default) or barlow (Barlow Twins, loss/barlow.py: per rank, no labels)
+        kind = cfg_get(cfg, "loss.kind", None) or "ntxent"
+        if kind == "barlow":
+            if self.supervised or cfg_get(cfg, "loss.gather", False) not in (None, False):
+                raise ValueError("loss.kind=barlow is not available with loss.supervised or "
+                                 "loss.gather")
+            self.loss_fn = BarlowTwins(lambd=cfg_get(cfg, "loss.barlow_lambda", 0.0051))
+        elif kind == "ntxent":
+            self.loss_fn = NTXent(temperature=cfg["parameter"]["temperature"],
+                                  gather=cfg_get(cfg, "loss.gather", False),
+                                  supervised=self.supervised)
+        else:
+            raise ValueError(f"loss.kind must be ntxent or barlow, got {kind!r}")
         # global negatives over RCCL: the fused head gathers z view by view under its GEMM 2
         # (models/head_fused.py _gemm2_pregather)
-        zg = self.loss_fn.gather is True and bool(st.comm)
+        zg = getattr(self.loss_fn, "gather", False) is True and bool(st.comm)
         for m in self.model.modules():
             if hasattr(m, "use_fused") and hasattr(m, "_seq"):
                 m._zgather = zg
