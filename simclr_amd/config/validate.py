@@ -39,7 +39,8 @@ LOSS_KINDS = ("ntxent", "barlow")
 
 def _check_loss_kind(cfg) -> None:
     """The opt-in ``loss.kind`` (``ntxent`` | ``barlow``, loss/barlow.py) and
-    ``loss.barlow_lambda``; Barlow Twins is per rank and has no labels."""
+    ``loss.barlow_lambda``; Barlow Twins has no labels and is per rank unless
+    ``loss.barlow_global`` (a boolean, only with ``barlow``) asks for the loss over all ranks."""
     loss = (cfg.get("loss") if hasattr(cfg, "get") else None) or {}
     kind = loss.get("kind")
     _check(kind is None or (isinstance(kind, str) and kind in LOSS_KINDS),
@@ -49,6 +50,10 @@ def _check_loss_kind(cfg) -> None:
         _check(isinstance(lam, (int, float)) and not isinstance(lam, bool),
                "loss.barlow_lambda must be a number")
         _check(lam > 0.0, "loss.barlow_lambda must be > 0")
+    glob = loss.get("barlow_global")
+    if glob is not None:
+        _check(isinstance(glob, bool), "loss.barlow_global must be a boolean")
+        _check(not glob or kind == "barlow", "loss.barlow_global=true needs loss.kind=barlow")
     if kind == "barlow":
         _check(not loss.get("supervised"),
                "loss.kind=barlow is not available with loss.supervised=true")

@@ -298,6 +298,164 @@ __global__ __launch_bounds__(256) void k_bt_std_bwd(const uint16_t* __restrict__
   }
 }
 
+// ---------------------------------------------------------------- the loss over all ranks
+// (loss.barlow_global: W ranks of n rows each, N = W·n; contract: loss/barlow.py.)  Between these
+// launches the ranks exchange [2][2][D] statistics (all-gather), the D x D slab (all-reduce) and
+// [2][2][D] column sums (all-gather); k_bt_corr, k_bt_loss (splits 1, n = N), k_bt_grad and
+// k_bt_bwd serve unchanged.
+
+// grid (D/64, 2 views), 1024 threads: the two passes of k_bt_standardize, same rows in the same
+// order; stats[0][v][d] = μ_r, stats[1][v][d] = M2_r = Σ_b (z − μ_r)² (not divided)
+template <typename T>
+__global__ __launch_bounds__(1024) void k_bt_stats(const T* __restrict__ z, int n, int D,
+                                                   float* __restrict__ stats) {
+#pragma clang fp contract(off)
+  __shared__ float red[BT_RG][64];
+  __shared__ float s_mu[64];
+  const int v = blockIdx.y, d0 = blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const T* zv = z + (size_t)v * n * D + d0 + tx;
+  float s = 0.f;
+  for (int b = ty; b < n; b += BT_RG) s += ldz(zv + (size_t)b * D);
+  red[ty][tx] = s;
+  __syncthreads();
+  if (ty == 0) {
+    float t = 0.f;
+    for (int k = 0; k < BT_RG; ++k) t += red[k][tx];
+    const float m = div_rn(t, (float)n);
+    s_mu[tx] = m;
+    stats[(size_t)v * D + d0 + tx] = m;
+  }
+  __syncthreads();
+  const float mu = s_mu[tx];
+  s = 0.f;
+  for (int b = ty; b < n; b += BT_RG) {
+    const float c = ldz(zv + (size_t)b * D) - mu;
+    s += c * c;
+  }
+  red[ty][tx] = s;
+  __syncthreads();
+  if (ty == 0) {
+    float t = 0.f;
+    for (int k = 0; k < BT_RG; ++k) t += red[k][tx];
+    stats[(size_t)(2 + v) * D + d0 + tx] = t;
+  }
+}
+
+// grid (D/64, 2 views), 1024 threads.  gst [W][2][2][D] are every rank's statistics in rank order:
+// μ = (Σ_r μ_r) / W, M2 = Σ_r (M2_r + n (μ_r − μ)²), both summed in rank order; σ² = M2 / N,
+// rstd as k_bt_standardize's, then its third pass on this rank's rows (ẑ and its transpose).
+// W = 1: μ = μ_0 / 1 and M2 = M2_0 + n · 0, the bits of k_bt_standardize.
+template <typename T>
+__global__ __launch_bounds__(1024) void k_bt_merge_standardize(const T* __restrict__ z,
+                                                               const float* __restrict__ gst,
+                                                               int W, int n, int D, float eps,
+                                                               float* __restrict__ rstd,
+                                                               uint16_t* __restrict__ zh,
+                                                               uint16_t* __restrict__ zhT) {
+#pragma clang fp contract(off)
+  __shared__ float s_mu[64], s_rs[64];
+  __shared__ uint16_t tile[64][34];  // [column][row of the 32-row chunk]
+  const int v = blockIdx.y, d0 = blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const T* zv = z + (size_t)v * n * D + d0 + tx;
+  if (ty == 0) {
+    const size_t rank_stride = (size_t)4 * D;
+    const float* pm = gst + (size_t)v * D + d0 + tx;        // μ_r
+    const float* pq = gst + (size_t)(2 + v) * D + d0 + tx;  // M2_r
+    float sm = pm[0];
+    for (int r = 1; r < W; ++r) sm += pm[r * rank_stride];
+    const float m = div_rn(sm, (float)W);
+    const float fn = (float)n;
+    float m2 = 0.f;
+    for (int r = 0; r < W; ++r) {
+      const float d = pm[r * rank_stride] - m;
+      const float t = pq[r * rank_stride] + fn * (d * d);
+      m2 = r == 0 ? t : m2 + t;
+    }
+    const float fN = (float)((long)W * n);
+    const float rs = div_rn(1.f, sqrt_rn(div_rn(m2, fN) + eps));
+    s_mu[tx] = m;
+    s_rs[tx] = rs;
+    rstd[(size_t)v * D + d0 + tx] = rs;
+  }
+  __syncthreads();
+  const float mu = s_mu[tx];
+  const float rs = s_rs[tx];
+  const int rl = threadIdx.x & 31, tc = threadIdx.x >> 5;  // the transposed write's row, column
+  for (int r0 = 0; r0 < n; r0 += 32) {
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int r = ty * 2 + k;
+      const uint16_t h = f2bf((ldz(zv + (size_t)(r0 + r) * D) - mu) * rs);
+      zh[(size_t)(v * n + r0 + r) * D + d0 + tx] = h;
+      tile[tx][r] = h;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int c = tc + 32 * k;
+      zhT[((size_t)v * D + d0 + c) * n + r0 + rl] = tile[c][rl];
+    }
+    __syncthreads();
+  }
+}
+
+// four consecutive entries per thread, as k_bt_loss: S = Σ_s slab_s in split order (not divided)
+__global__ __launch_bounds__(256) void k_bt_slab_merge(const float* __restrict__ part, int splits,
+                                                       int D, float* __restrict__ S) {
+  const size_t i4 = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t n4 = (size_t)D * D / 4;
+  const float4* p = (const float4*)part;
+  float4 a = p[i4];
+  for (int s = 1; s < splits; ++s) {
+    const float4 x = p[(size_t)s * n4 + i4];
+    a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w;
+  }
+  ((float4*)S)[i4] = a;
+}
+
+// one thread per (view, dẑ | dẑ·ẑ, column), 4 D of them (a multiple of 256): the row tiles'
+// partials of k_bt_bwd in tile order, as k_bt_std_bwd sums them; csum [2][2][D]
+__global__ __launch_bounds__(256) void k_bt_colsum(const float* __restrict__ colpart, int MT, int D,
+                                                   float* __restrict__ csum) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const int col = i % D, which = (i / D) & 1, v = i / (2 * D);
+  float s = 0.f;
+  for (int t = 0; t < MT; ++t) s += colpart[((size_t)(v * MT + t) * 2 + which) * D + col];
+  csum[i] = s;
+}
+
+// grid (D/64, n/32, 2 views): k_bt_std_bwd with the means over all N rows: every block adds its
+// 64 columns' sums of the W ranks (gsum [W][2][2][D]) in rank order and divides by N
+__global__ __launch_bounds__(256) void k_bt_std_bwd_global(const uint16_t* __restrict__ zh,
+                                                           const float* __restrict__ rstd,
+                                                           const float* __restrict__ dzh,
+                                                           const float* __restrict__ gsum, int W,
+                                                           int n, int D,
+                                                           uint16_t* __restrict__ dz_bf16,
+                                                           float* __restrict__ dz_f32) {
+  __shared__ float m[2][64];
+  const int v = blockIdx.z, d0 = blockIdx.x * 64, r0 = blockIdx.y * 32;
+  if (threadIdx.x < 128) {
+    const int which = threadIdx.x >> 6, col = threadIdx.x & 63;
+    float s = 0.f;
+    for (int r = 0; r < W; ++r) s += gsum[((size_t)(r * 2 + v) * 2 + which) * D + d0 + col];
+    m[which][col] = s / (float)((long)W * n);
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const float m1 = m[0][tx], m2 = m[1][tx];
+  const float rs = rstd[(size_t)v * D + d0 + tx];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const size_t i = (size_t)(v * n + r0 + ty * 8 + k) * D + d0 + tx;
+    const float val = rs * ((dzh[i] - m1) - bf2f(zh[i]) * m2);
+    if (dz_bf16) dz_bf16[i] = f2bf(val);
+    if (dz_f32) dz_f32[i] = val;
+  }
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------- host API (raw pointers)
@@ -361,5 +519,47 @@ void barlow_std_backward(const uint16_t* zh, const float* rstd, const float* dzh
                          hipStream_t s) {
   hipLaunchKernelGGL(k_bt_std_bwd, dim3(D / 64, n / 32, 2), dim3(256), 0, s, zh, rstd, dzh,
                      colpart, n, D, dz_bf16, dz_f32);
+  HIP_CHECK_LAUNCH();
+}
+
+// ---- the loss over all ranks (W ranks, N = W · n rows)
+void barlow_stats(const void* z, int z_f32, int n, int D, float* stats, hipStream_t s) {
+  const dim3 grid(D / 64, 2), block(1024);
+  if (z_f32)
+    hipLaunchKernelGGL(k_bt_stats<float>, grid, block, 0, s, (const float*)z, n, D, stats);
+  else
+    hipLaunchKernelGGL(k_bt_stats<uint16_t>, grid, block, 0, s, (const uint16_t*)z, n, D, stats);
+  HIP_CHECK_LAUNCH();
+}
+
+void barlow_merge_standardize(const void* z, int z_f32, const float* gstats, int W, int n, int D,
+                              float eps, float* rstd, uint16_t* zh, uint16_t* zhT,
+                              hipStream_t s) {
+  const dim3 grid(D / 64, 2), block(1024);
+  if (z_f32)
+    hipLaunchKernelGGL(k_bt_merge_standardize<float>, grid, block, 0, s, (const float*)z, gstats,
+                       W, n, D, eps, rstd, zh, zhT);
+  else
+    hipLaunchKernelGGL(k_bt_merge_standardize<uint16_t>, grid, block, 0, s, (const uint16_t*)z,
+                       gstats, W, n, D, eps, rstd, zh, zhT);
+  HIP_CHECK_LAUNCH();
+}
+
+void barlow_slab_merge(const float* part, int splits, int D, float* S, hipStream_t s) {
+  hipLaunchKernelGGL(k_bt_slab_merge, dim3(barlow_loss_blocks(D)), dim3(256), 0, s, part, splits,
+                     D, S);
+  HIP_CHECK_LAUNCH();
+}
+
+void barlow_colsum(const float* colpart, int n, int D, float* csum, hipStream_t s) {
+  hipLaunchKernelGGL(k_bt_colsum, dim3(4 * D / 256), dim3(256), 0, s, colpart, n / 32, D, csum);
+  HIP_CHECK_LAUNCH();
+}
+
+void barlow_std_backward_global(const uint16_t* zh, const float* rstd, const float* dzh,
+                                const float* gsum, int W, int n, int D, uint16_t* dz_bf16,
+                                float* dz_f32, hipStream_t s) {
+  hipLaunchKernelGGL(k_bt_std_bwd_global, dim3(D / 64, n / 32, 2), dim3(256), 0, s, zh, rstd, dzh,
+                     gsum, W, n, D, dz_bf16, dz_f32);
   HIP_CHECK_LAUNCH();
 }

@@ -1017,6 +1017,80 @@ void bt_std_backward(const Tensor& zh, const Tensor& rstd, const Tensor& dzh,
   barlow_std_backward(bf(zh, "zh"), f32(rstd, "rstd"), f32(dzh, "dzh"), f32(colpart, "colpart"),
                       (int)n, (int)D, ob, of, cur_stream());
 }
+// the loss over W ranks (loss.barlow_global): W is the leading size of the gathered tensors
+void check_bt_world(int64_t W, int64_t n, const char* what) {
+  TORCH_CHECK(W >= 1 && W <= 1024 && W * n <= (1 << 20), what, ": W ranks of n rows need "
+              "1 <= W <= 1024 and W * n <= 2^20, got W ", W, ", n ", n);
+}
+void check_bt_z(const Tensor& z, const char* what) {
+  TORCH_CHECK(z.dim() == 2 && z.size(0) % 2 == 0, what, ": z must be [2n][D]");
+  check_bt(z.size(0) / 2, z.size(1));
+  TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
+                  (z.scalar_type() == at::kBFloat16 || z.scalar_type() == at::kFloat),
+              what, ": z must be a contiguous bf16 or fp32 GPU tensor");
+}
+void bt_stats(const Tensor& z, const Tensor& stats) {
+  check_bt_z(z, "bt_stats");
+  const int64_t n = z.size(0) / 2, D = z.size(1);
+  TORCH_CHECK(stats.numel() == 4 * D, "bt_stats: stats must be [2][2][D] = ", 4 * D,
+              " values, got ", stats.numel());
+  barlow_stats(z.data_ptr(), z.scalar_type() == at::kFloat ? 1 : 0, (int)n, (int)D,
+               f32w(stats, "stats"), cur_stream());
+}
+void bt_merge_standardize(const Tensor& z, const Tensor& gstats, double eps, const Tensor& rstd,
+                          const Tensor& zh, const Tensor& zhT) {
+  check_bt_z(z, "bt_merge_standardize");
+  const int64_t n = z.size(0) / 2, D = z.size(1);
+  TORCH_CHECK(gstats.dim() == 4 && gstats.size(1) == 2 && gstats.size(2) == 2 &&
+                  gstats.size(3) == D,
+              "bt_merge_standardize: gstats must be [W][2][2][D] with D = ", D);
+  const int64_t W = gstats.size(0);
+  check_bt_world(W, n, "bt_merge_standardize");
+  TORCH_CHECK(eps > 0.0, "bt_merge_standardize: eps must be > 0");
+  TORCH_CHECK(rstd.numel() == 2 * D && zh.numel() == 2 * n * D && zhT.numel() == 2 * n * D,
+              "bt_merge_standardize sizes: rstd [2][D], zh [2n][D], zhT [2][D][n]");
+  barlow_merge_standardize(z.data_ptr(), z.scalar_type() == at::kFloat ? 1 : 0,
+                           f32(gstats, "gstats"), (int)W, (int)n, (int)D, (float)eps,
+                           f32w(rstd, "rstd"), bfw(zh, "zh"), bfw(zhT, "zhT"), cur_stream());
+}
+void bt_slab_merge(const Tensor& part, int64_t splits, const Tensor& S) {
+  TORCH_CHECK(S.dim() == 2 && S.size(0) == S.size(1), "bt_slab_merge: S is [D][D]");
+  const int64_t D = S.size(0);
+  check_bt(32, D);
+  TORCH_CHECK(splits >= 1 && part.numel() == splits * D * D,
+              "bt_slab_merge: part must be [splits][D][D]");
+  barlow_slab_merge(f32(part, "part"), (int)splits, (int)D, f32w(S, "S"), cur_stream());
+}
+void bt_colsum(const Tensor& colpart, const Tensor& csum) {
+  TORCH_CHECK(colpart.dim() == 4 && colpart.size(0) == 2 && colpart.size(2) == 2,
+              "bt_colsum: colpart must be [2][n/32][2][D]");
+  const int64_t n = colpart.size(1) * 32, D = colpart.size(3);
+  check_bt(n, D);
+  TORCH_CHECK(csum.numel() == 4 * D, "bt_colsum: csum must be [2][2][D] = ", 4 * D,
+              " values, got ", csum.numel());
+  barlow_colsum(f32(colpart, "colpart"), (int)n, (int)D, f32w(csum, "csum"), cur_stream());
+}
+void bt_std_backward_global(const Tensor& zh, const Tensor& rstd, const Tensor& dzh,
+                            const Tensor& gsum, const c10::optional<Tensor>& dz_bf16,
+                            const c10::optional<Tensor>& dz_f32) {
+  TORCH_CHECK(zh.dim() == 2 && zh.size(0) % 2 == 0, "bt_std_backward_global: zh must be [2n][D]");
+  const int64_t n = zh.size(0) / 2, D = zh.size(1);
+  check_bt(n, D);
+  TORCH_CHECK(gsum.dim() == 4 && gsum.size(1) == 2 && gsum.size(2) == 2 && gsum.size(3) == D,
+              "bt_std_backward_global: gsum must be [W][2][2][D] with D = ", D);
+  const int64_t W = gsum.size(0);
+  check_bt_world(W, n, "bt_std_backward_global");
+  TORCH_CHECK(rstd.numel() == 2 * D && dzh.numel() == 2 * n * D,
+              "bt_std_backward_global sizes: rstd [2][D], dzh [2n][D]");
+  uint16_t* ob = optbfw(dz_bf16, "dz_bf16");
+  float* of = optf32w(dz_f32, "dz_f32");
+  TORCH_CHECK((ob != nullptr) != (of != nullptr),
+              "bt_std_backward_global: one of dz_bf16 / dz_f32");
+  TORCH_CHECK((ob ? dz_bf16->numel() : dz_f32->numel()) == 2 * n * D,
+              "bt_std_backward_global: dz size");
+  barlow_std_backward_global(bf(zh, "zh"), f32(rstd, "rstd"), f32(dzh, "dzh"), f32(gsum, "gsum"),
+                             (int)W, (int)n, (int)D, ob, of, cur_stream());
+}
 
 // ------------------------------------------------------------------------------- lars
 void lars_norms_op(const Tensor& p, const Tensor& g, const Tensor& chunk_beg,
@@ -1627,6 +1701,11 @@ TORCH_LIBRARY(simclr_amd, m) {
   m.def("bt_grad(Tensor C, float lambd, Tensor gout, Tensor(a!) G, Tensor(b!) GT) -> ()", &bt_grad);
   m.def("bt_backward(Tensor zh, Tensor G, Tensor GT, Tensor(a!) dzh, Tensor(b!) colpart) -> ()", &bt_backward);
   m.def("bt_std_backward(Tensor zh, Tensor rstd, Tensor dzh, Tensor colpart, Tensor(a!)? dz_bf16, Tensor(b!)? dz_f32) -> ()", &bt_std_backward);
+  m.def("bt_stats(Tensor z, Tensor(a!) stats) -> ()", &bt_stats);
+  m.def("bt_merge_standardize(Tensor z, Tensor gstats, float eps, Tensor(a!) rstd, Tensor(b!) zh, Tensor(c!) zhT) -> ()", &bt_merge_standardize);
+  m.def("bt_slab_merge(Tensor part, int splits, Tensor(a!) S) -> ()", &bt_slab_merge);
+  m.def("bt_colsum(Tensor colpart, Tensor(a!) csum) -> ()", &bt_colsum);
+  m.def("bt_std_backward_global(Tensor zh, Tensor rstd, Tensor dzh, Tensor gsum, Tensor(a!)? dz_bf16, Tensor(b!)? dz_f32) -> ()", &bt_std_backward_global);
   m.def("lars_norms(Tensor p, Tensor g, Tensor chunk_beg, Tensor chunk_end, float grad_scale, Tensor(a!) norms) -> ()", &lars_norms_op);
   m.def("lars_update(Tensor(a!) p, Tensor g, Tensor(b!) mom, Tensor(c!)? shadow, Tensor chunk_seg, Tensor chunk_beg, Tensor chunk_end, Tensor seg_chunk_beg, Tensor seg_chunk_end, Tensor seg_wd, Tensor seg_flags, Tensor norms, Tensor lr, float momentum, float trust, float eps, float grad_scale, bool nesterov) -> ()", &lars_update_op);
   m.def("lr_step(Tensor(a!) step, Tensor(b!) lr, float lr0, int warmup, int total, int mode) -> ()", &lr_step_op);

@@ -261,6 +261,18 @@ void barlow_backward(const uint16_t* zh, const uint16_t* G, const uint16_t* GT, 
 void barlow_std_backward(const uint16_t* zh, const float* rstd, const float* dzh,
                          const float* colpart, int n, int D, uint16_t* dz_bf16, float* dz_f32,
                          hipStream_t s);
+// the loss over W ranks of n rows each (loss.barlow_global), around three collectives:
+// stats [2][2][D] = (μ_r, M2_r) per view; gstats [W][2][2][D] the all-gathered ones, merged in
+// rank order into rstd, zh, zhT; S [D][D] = Σ part in split order (undivided, to be all-reduced);
+// csum [2][2][D] = colpart summed in tile order; gsum [W][2][2][D] the all-gathered ones
+void barlow_stats(const void* z, int z_f32, int n, int D, float* stats, hipStream_t s);
+void barlow_merge_standardize(const void* z, int z_f32, const float* gstats, int W, int n, int D,
+                              float eps, float* rstd, uint16_t* zh, uint16_t* zhT, hipStream_t s);
+void barlow_slab_merge(const float* part, int splits, int D, float* S, hipStream_t s);
+void barlow_colsum(const float* colpart, int n, int D, float* csum, hipStream_t s);
+void barlow_std_backward_global(const uint16_t* zh, const float* rstd, const float* dzh,
+                                const float* gsum, int W, int n, int D, uint16_t* dz_bf16,
+                                float* dz_f32, hipStream_t s);
 
 // ---- lars.hip (flat fp32 master / grad / momentum, bf16 shadow; per-segment table)
 void lars_norms(const float* p, const float* g, const int* chunk_beg, const int* chunk_end,

@@ -25,17 +25,44 @@ The contract, identical in the kernels of ``csrc/barlow.hip`` and in :func:`barl
   this loss captures as one with NT-Xent does.
 * HIP path: ``n % 32 == 0``, ``D % 64 == 0``, ``64 <= D <= 2048`` and ``registry.use_hip(z)``;
   anything else takes the twin (unrounded, in fp32; fp64 for a ``double`` z).
-* Data-parallel runs: the loss is per rank (each rank correlates its own n images) and the
-  gradients are averaged by the flat store's buckets; an all-reduced C is not implemented.
+* Data-parallel runs: by default the loss is per rank (each rank correlates its own n images)
+  and the gradients are averaged by the flat store's buckets.
+
+``global_batch`` (``loss.barlow_global``): the loss of the global batch, as the paper defines it.
+W ranks hold z_r ``[2n][D]`` with the same n, N = W·n; three collectives per step:
+
+1. Local statistics per rank, view and column, in fp32 and :func:`_row_sum`'s order:
+   ``μ_r = (1/n) Σ_b z`` (quotient through fp64), then ``M2_r = Σ_b (z − μ_r)²``, not divided.
+2. One all-gather of ``[2][2][D]`` (μ_r, M2_r) gives ``[W][2][2][D]``; every rank merges it in
+   rank order in fp32: ``μ = (Σ_r μ_r) / W``, ``M2 = Σ_r (M2_r + n·(μ_r − μ)²)``, ``σ² = M2 / N``,
+   quotients and ``rstd = 1 / sqrt(σ² + eps)`` through fp64; ``ẑ = (z − μ)·rstd``, rounded once to
+   bf16 on the HIP path and by the rounded twin.  A column constant over the global batch gives
+   ẑ = 0 (exactly when W·μ_r is representable: always for W a power of two), never NaN; one
+   constant within each rank but not between them has ``M2_r = 0`` and σ² from the mean term.
+3. ``S_r = ẑ0ᵀ ẑ1`` over the rank's n rows (slabs merged in split order, not divided), one fp32
+   SUM all-reduce of ``[D][D]``, ``C = S / N``, the loss as above.  Every rank has the same value.
+4. Backward: a rank returns ``dz_r = W · ∂L/∂z_r``, so that the gradient buckets' mean over the
+   ranks is the gradient of the global loss (the true gradient, not the authors' DDP code's,
+   which is off by W).  G from C as above; ``dẑ0 = ẑ1·Gᵀ / n``, ``dẑ1 = ẑ0·G / n`` with the LOCAL n
+   (= W/N); the per-view column sums of dẑ and dẑ·ẑ, ``[2][2][D]`` in tile order, are all-gathered
+   and added in rank order; ``dz = rstd·(dẑ − Σ/N − ẑ·Σ/N)``.
+5. W = 1 (a forced 1-rank group): loss, C and dz are bit for bit the per-rank path's, in the
+   kernels, in the rounded twin and in the unrounded one (which, for autograd's dz to keep its
+   bits, forms ẑ as ``(c_r − (μ − μ_r))·rstd`` from the rank's centred rows ``c_r = z − μ_r``).
+6. No atomics, no per-step host value in a launch; every collective is a ``torch.distributed``
+   call on ``pstate``'s group, issued on the current stream (the chain is serial).  Repeatable
+   up to the all-reduce's own order.  The one-shot IPC exchange is not used.
 """
 from __future__ import annotations
 
 from typing import Optional
 
 import torch
+import torch.distributed as dist
 from torch import nn
 
 from ..ops import registry
+from ..parallel import state as pstate
 
 
 def _bf16_round(x: torch.Tensor) -> torch.Tensor:
@@ -77,6 +104,53 @@ def _standardize(zf: torch.Tensor, n: int, eps: float):
     return c * rstd, rstd
 
 
+def _local_stats(zf: torch.Tensor, n: int) -> torch.Tensor:
+    """zf [2n][D] -> [2][2][D]: [0] = μ_r, [1] = M2_r = Σ_b (z − μ_r)² per view (not divided), the
+    values ``_standardize`` forms before its division (``k_bt_stats``)."""
+    zv = zf.view(2, n, zf.shape[1])
+    mu = (_row_sum(zv).double() / n).to(zf.dtype)
+    c = zv - mu
+    return torch.stack([mu.squeeze(1), _row_sum(c * c).squeeze(1)])
+
+
+def _merge_moments(gst: torch.Tensor, n: int):
+    """gst [W][2][2][D], every rank's (μ_r, M2_r) in rank order -> μ, σ² [2][D] of the W·n rows:
+    the rank-order merge of the contract (``k_bt_merge_standardize``)."""
+    W, dt = gst.shape[0], gst.dtype
+    sm = gst[0, 0]
+    for r in range(1, W):
+        sm = sm + gst[r, 0]
+    mu = (sm.double() / W).to(dt)
+    m2 = None
+    for r in range(W):
+        d = gst[r, 0] - mu
+        t = gst[r, 1] + n * (d * d)
+        m2 = t if m2 is None else m2 + t
+    return mu, (m2.double() / (W * n)).to(dt)
+
+
+def _merge_stats(gst: torch.Tensor, n: int, eps: float):
+    """:func:`_merge_moments`, then rstd as ``_standardize``'s -> μ, rstd [2][1][D]."""
+    mu, var = _merge_moments(gst, n)
+    rstd = (1.0 / torch.sqrt((var + eps).double()).to(gst.dtype).double()).to(gst.dtype)
+    return mu.unsqueeze(1), rstd.unsqueeze(1)
+
+
+def _rank_sum(g: torch.Tensor) -> torch.Tensor:
+    """g [W][...] -> the W blocks added in rank order."""
+    tot = g[0]
+    for r in range(1, g.shape[0]):
+        tot = tot + g[r]
+    return tot
+
+
+def _gather(x: torch.Tensor, world_size: int, group) -> torch.Tensor:
+    """x -> [W][*x.shape], every rank's x in rank order (not differentiable)."""
+    out = torch.empty((world_size, *x.shape), device=x.device, dtype=x.dtype)
+    dist.all_gather_into_tensor(out.view(-1), x.contiguous().view(-1), group=group)  # (flat: gloo)
+    return out
+
+
 def _loss_terms(C: torch.Tensor, lambd: float) -> torch.Tensor:
     eye = torch.eye(C.shape[0], dtype=torch.bool, device=C.device)
     om = 1.0 - C
@@ -110,15 +184,82 @@ class _BarlowTwinFn(torch.autograd.Function):
         return dz.reshape(2 * n, -1).to(zdtype), None, None, None
 
 
+class _BarlowGlobalTwinFn(torch.autograd.Function):
+    """The rounded twin over all ranks: :class:`_BarlowTwinFn` with the three exchanges of the
+    contract (statistics, the slab, the column sums) at the kernels' points."""
+
+    @staticmethod
+    def forward(ctx, z, n, lambd, eps, group, W):
+        zf = z.float()
+        gst = _gather(_local_stats(zf, n), W, group)
+        mu, rstd = _merge_stats(gst, n, eps)
+        zh = _bf16_round((zf.view(2, n, -1) - mu) * rstd)
+        S = (zh[0].t() @ zh[1]).contiguous()
+        dist.all_reduce(S, group=group)
+        C = S / (W * n)
+        ctx.save_for_backward(zh, rstd, C)
+        ctx.cfg = (n, lambd, z.dtype, group, W)
+        ctx.mark_non_differentiable(C)
+        return _loss_terms(C, lambd), C
+
+    @staticmethod
+    def backward(ctx, gout, _gc):
+        zh, rstd, C = ctx.saved_tensors
+        n, lambd, zdtype, group, W = ctx.cfg
+        g = gout.float()
+        eye = torch.eye(C.shape[0], dtype=torch.bool, device=C.device)
+        G = _bf16_round(torch.where(eye, (-2.0 * g) * (1.0 - C), (2.0 * g * lambd) * C))
+        dzh = torch.stack([zh[1] @ G.t(), zh[0] @ G]) / n
+        csum = torch.stack([dzh.sum(dim=1), (dzh * zh).sum(dim=1)], dim=1)  # [2 views][2][D]
+        tot = _rank_sum(_gather(csum, W, group))
+        m1 = tot[:, 0:1] / (W * n)
+        m2 = tot[:, 1:2] / (W * n)
+        dz = rstd * ((dzh - m1) - zh * m2)
+        return dz.reshape(2 * n, -1).to(zdtype), None, None, None, None, None
+
+
+def _global_plain(z: torch.Tensor, n: int, lambd: float, eps: float, group, W: int):
+    """The unrounded loss over all ranks on differentiable ops and differentiable collectives:
+    every rank backpropagates its identical loss, so their backward yields W · ∂L/∂z_r.
+    ẑ is formed from the rank's own centred rows, ``(c_r − (μ − μ_r))·rstd`` with
+    ``c_r = z − μ_r`` (the c_r that M2_r is summed from): the same value as ``(z − μ)·rstd`` up to
+    one rounding, and on a 1-rank group (μ − μ_r = 0) the per-rank path's graph, so that the
+    loss, C and autograd's dz have its bits."""
+    from torch.distributed.nn.functional import all_gather, all_reduce
+    zf = z if z.dtype == torch.float64 else z.float()
+    zv = zf.view(2, n, -1)
+    mu_r = (_row_sum(zv).double() / n).to(zf.dtype)
+    c = zv - mu_r
+    stats = torch.stack([mu_r.squeeze(1), _row_sum(c * c).squeeze(1)])  # as _local_stats
+    gst = torch.stack(all_gather(stats, group=group))
+    mu, rstd = _merge_stats(gst, n, eps)
+    zh = (c - (mu - mu_r)) * rstd
+    S = all_reduce((zh[0].t() @ zh[1]).contiguous(), group=group)
+    C = S / (W * n)
+    return _loss_terms(C, lambd), C
+
+
 def barlow_twins_torch(z: torch.Tensor, n: int, lambd: float, eps: float = 1e-5,
-                       round_operands: bool = False, return_c: bool = False):
+                       round_operands: bool = False, return_c: bool = False, group=None,
+                       world_size: int = 1, rank: int = 0):
     """The loss on torch ops; ``z`` = [view0; view1] of shape [2n, D].  Without
     ``round_operands`` these are plain differentiable ops (a ``double`` z gives the fp64 oracle);
     with it, an explicit function that rounds ẑ and G to bf16 where the kernels do.
-    ``return_c``: also return C (not differentiable with ``round_operands``)."""
+    ``return_c``: also return C (not differentiable with ``round_operands``).
+    ``group`` / ``world_size`` / ``rank`` (as ``nt_xent_torch``): with a group or more than one
+    rank, the loss of the global batch of ``world_size`` · n images (module docstring); every
+    rank passes its own z and gets the same loss, and dz = world_size · ∂loss/∂z.  ``rank`` is
+    accepted for the signature of ``nt_xent_torch`` only: every exchange is symmetric in the
+    ranks (all-gather, all-reduce), so nothing here depends on it."""
     if z.dim() != 2 or z.shape[0] != 2 * n:
         raise ValueError(f"z must be [2n][D] with n = {n}, got {tuple(z.shape)}")
-    if round_operands:
+    if group is not None or world_size > 1:
+        if round_operands:
+            loss, C = _BarlowGlobalTwinFn.apply(z, n, float(lambd), float(eps), group,
+                                                int(world_size))
+        else:
+            loss, C = _global_plain(z, n, float(lambd), float(eps), group, int(world_size))
+    elif round_operands:
         loss, C = _BarlowTwinFn.apply(z, n, float(lambd), float(eps))
     else:
         zh, _ = _standardize(z if z.dtype == torch.float64 else z.float(), n, eps)
@@ -178,6 +319,77 @@ class _BarlowHipFn(torch.autograd.Function):
         return dz, None, None, None
 
 
+class _BarlowGlobalHipFn(torch.autograd.Function):
+    """The loss over all ranks: ten launches (nine with a single slab; the per-rank path has
+    seven: stats + merge replace standardise, the slab merge is new, colsum + the global std
+    backward replace the std backward) and three collectives on the current stream
+    (statistics all-gather, slab all-reduce, column-sum all-gather); ``bt_corr``, ``bt_loss``
+    (one slab, n = N), ``bt_grad`` and ``bt_backward`` are the per-rank path's."""
+
+    @staticmethod
+    def forward(ctx, z, n, lambd, eps, st):
+        from ..ops import _ext
+        ops = _ext.ops()
+        D = z.shape[1]
+        dev = z.device
+        W = st.world_size
+        zc = z.contiguous()
+        stats = torch.empty((2, 2, D), device=dev, dtype=torch.float32)
+        ops.bt_stats(zc, stats)
+        gstats = torch.empty((W, 2, 2, D), device=dev, dtype=torch.float32)
+        dist.all_gather_into_tensor(gstats.view(-1), stats.view(-1), group=st.group)
+        rstd = torch.empty((2, D), device=dev, dtype=torch.float32)
+        zh = torch.empty((2 * n, D), device=dev, dtype=torch.bfloat16)
+        zhT = torch.empty((2, D, n), device=dev, dtype=torch.bfloat16)
+        ops.bt_merge_standardize(zc, gstats, eps, rstd, zh, zhT)
+        splits = ops.bt_corr_splits(n, D)
+        part = torch.empty((splits, D, D), device=dev, dtype=torch.float32)
+        ops.bt_corr(zhT, n, splits, part)
+        if splits > 1:
+            S = torch.empty((D, D), device=dev, dtype=torch.float32)
+            ops.bt_slab_merge(part, splits, S)
+        else:
+            S = part.view(D, D)  # (the single slab is S_r already)
+        dist.all_reduce(S, group=st.group)
+        C = torch.empty((D, D), device=dev, dtype=torch.float32)
+        lpart = torch.empty((ops.bt_loss_blocks(D),), device=dev, dtype=torch.float32)
+        ops.bt_loss(S, 1, W * n, lambd, C, lpart)
+        out = torch.empty((1,), device=dev, dtype=torch.float32)
+        ops.nt_reduce_loss(lpart, 1.0, out)
+        ctx.save_for_backward(zh, rstd, C)
+        ctx.cfg = (n, lambd, z.dtype, st)
+        ctx.mark_non_differentiable(C)
+        return out.view(()), C
+
+    @staticmethod
+    def backward(ctx, gout, _gc):
+        from ..ops import _ext
+        ops = _ext.ops()
+        zh, rstd, C = ctx.saved_tensors
+        n, lambd, zdtype, st = ctx.cfg
+        D = zh.shape[1]
+        dev = zh.device
+        W = st.world_size
+        g = gout.reshape(1).float().contiguous()
+        G = torch.empty((D, D), device=dev, dtype=torch.bfloat16)
+        GT = torch.empty((D, D), device=dev, dtype=torch.bfloat16)
+        ops.bt_grad(C, lambd, g, G, GT)
+        dzh = torch.empty((2 * n, D), device=dev, dtype=torch.float32)
+        colpart = torch.empty((2, n // 32, 2, D), device=dev, dtype=torch.float32)
+        ops.bt_backward(zh, G, GT, dzh, colpart)
+        csum = torch.empty((2, 2, D), device=dev, dtype=torch.float32)
+        ops.bt_colsum(colpart, csum)
+        gsum = torch.empty((W, 2, 2, D), device=dev, dtype=torch.float32)
+        dist.all_gather_into_tensor(gsum.view(-1), csum.view(-1), group=st.group)
+        if zdtype == torch.bfloat16:
+            dz = torch.empty((2 * n, D), device=dev, dtype=torch.bfloat16)
+            ops.bt_std_backward_global(zh, rstd, dzh, gsum, dz, None)
+        else:
+            dz = torch.empty((2 * n, D), device=dev, dtype=torch.float32)
+            ops.bt_std_backward_global(zh, rstd, dzh, gsum, None, dz)
+        return dz, None, None, None, None
+
+
 def hip_path(z: torch.Tensor, n: int) -> bool:
     """Whether ``z`` = [2n][D] takes the kernels (the limits in the module docstring)."""
     D = z.shape[1]
@@ -186,9 +398,11 @@ def hip_path(z: torch.Tensor, n: int) -> bool:
 
 
 class BarlowTwins(nn.Module):
-    def __init__(self, lambd: float = 0.0051, eps: float = 1e-5):
+    def __init__(self, lambd: float = 0.0051, eps: float = 1e-5, global_batch: bool = False):
         """``lambd``: the weight of the off-diagonal (redundancy) term, the paper's 0.0051;
-        ``eps``: the standardisation's, BatchNorm1d's 1e-5."""
+        ``eps``: the standardisation's, BatchNorm1d's 1e-5; ``global_batch``
+        (``loss.barlow_global``): with a data-parallel group, the loss of all ranks' images
+        (module docstring) instead of the per-rank one."""
         if not lambd > 0.0:
             raise ValueError(f"loss.barlow_lambda must be > 0, got {lambd}")
         if not eps > 0.0:
@@ -196,6 +410,7 @@ class BarlowTwins(nn.Module):
         super().__init__()
         self.lambd = float(lambd)
         self.eps = float(eps)
+        self.global_batch = bool(global_batch)
 
     def forward(self, view0: torch.Tensor, view1: Optional[torch.Tensor] = None,
                 return_c: bool = False):
@@ -209,6 +424,13 @@ class BarlowTwins(nn.Module):
             n = z.shape[0] // 2
         if z.dim() != 2 or z.shape[0] != 2 * n:
             raise ValueError(f"z must be [2n][D], got {tuple(z.shape)}")
+        st = pstate.get()
+        if self.global_batch and st.comm:
+            if hip_path(z, n):
+                loss, C = _BarlowGlobalHipFn.apply(z, n, self.lambd, self.eps, st)
+                return (loss, C) if return_c else loss
+            return barlow_twins_torch(z, n, self.lambd, self.eps, return_c=return_c,
+                                      group=st.group, world_size=st.world_size, rank=st.rank)
         if hip_path(z, n):
             loss, C = _BarlowHipFn.apply(z, n, self.lambd, self.eps)
             return (loss, C) if return_c else loss

@@ -102,7 +102,10 @@ class Trainer:
             if self.supervised or cfg_get(cfg, "loss.gather", False) not in (None, False):
                 raise ValueError("loss.kind=barlow is not available with loss.supervised or "
                                  "loss.gather")
-            self.loss_fn = BarlowTwins(lambd=cfg_get(cfg, "loss.barlow_lambda", 0.0051))
+            # loss.barlow_global: statistics and C over all ranks' images (three collectives)
+            self.loss_fn = BarlowTwins(lambd=cfg_get(cfg, "loss.barlow_lambda", 0.0051),
+                                       global_batch=bool(cfg_get(cfg, "loss.barlow_global",
+                                                                 False)))
         elif kind == "ntxent":
             self.loss_fn = NTXent(temperature=cfg["parameter"]["temperature"],
                                   gather=cfg_get(cfg, "loss.gather", False),
