@@ -34,12 +34,38 @@ def _check_supervised(cfg) -> None:
            "loss.supervised=true is not available with loss.gather=ring")
 
 
-LOSS_KINDS = ("ntxent", "barlow")
+LOSS_KINDS = ("ntxent", "barlow", "nnclr")
+NN_QUEUE_DEFAULT = 16384
+NN_QUEUE_MULTIPLE, NN_QUEUE_MAX = 256, 131072
+
+
+def _check_nnclr(cfg, loss, kind) -> None:
+    """``loss.kind=nnclr`` (loss/nnclr.py: per rank, no labels, no gather) and its support-set
+    size ``loss.nn_queue``: a multiple of 256 in [256, 131072], at least ``experiment.batches``;
+    the key is valid with ``nnclr`` only."""
+    q = loss.get("nn_queue")
+    if q is not None:
+        _check(kind == "nnclr", "loss.nn_queue needs loss.kind=nnclr")
+        _check(isinstance(q, int) and not isinstance(q, bool), "loss.nn_queue must be an integer")
+        _check(NN_QUEUE_MULTIPLE <= q <= NN_QUEUE_MAX and q % NN_QUEUE_MULTIPLE == 0,
+               f"loss.nn_queue must be a multiple of {NN_QUEUE_MULTIPLE} in "
+               f"[{NN_QUEUE_MULTIPLE}, {NN_QUEUE_MAX}]")
+    if kind != "nnclr":
+        return
+    _check(not loss.get("supervised"),
+           "loss.kind=nnclr is not available with loss.supervised=true")
+    _check(loss.get("gather") in (None, False),
+           "loss.kind=nnclr is not available with loss.gather (the loss is per rank)")
+    _check(not loss.get("barlow_global"),
+           "loss.kind=nnclr is not available with loss.barlow_global=true")
+    batches = cfg["experiment"]["batches"]
+    _check((NN_QUEUE_DEFAULT if q is None else q) >= batches,
+           f"loss.nn_queue must be at least experiment.batches ({batches})")
 
 
 def _check_loss_kind(cfg) -> None:
-    """The opt-in ``loss.kind`` (``ntxent`` | ``barlow``, loss/barlow.py) and
-    ``loss.barlow_lambda``; Barlow Twins has no labels and is per rank unless
+    """The opt-in ``loss.kind`` (``ntxent`` | ``barlow``, loss/barlow.py | ``nnclr``,
+    loss/nnclr.py) and ``loss.barlow_lambda``; Barlow Twins has no labels and is per rank unless
     ``loss.barlow_global`` (a boolean, only with ``barlow``) asks for the loss over all ranks."""
     loss = (cfg.get("loss") if hasattr(cfg, "get") else None) or {}
     kind = loss.get("kind")
@@ -59,6 +85,7 @@ def _check_loss_kind(cfg) -> None:
                "loss.kind=barlow is not available with loss.supervised=true")
         _check(loss.get("gather") in (None, False),
                "loss.kind=barlow is not available with loss.gather (the loss is per rank)")
+    _check_nnclr(cfg, loss, kind)
 
 
 def _check_online_probe(cfg) -> None:

@@ -935,6 +935,115 @@ void nt_expand_labels(const Tensor& labels, const c10::optional<Tensor>& idx, in
                        (int)views, out.data_ptr<int>(), cur_stream());
 }
 
+// ------------------------------------------------------------------------------- nnclr
+// (csrc/nnclr.hip; every tensor's size is checked against n, D and Q before any launch)
+void check_nc(int64_t n, int64_t D, const char* what) {
+  TORCH_CHECK(n >= 16 && n % 16 == 0 && n <= (1 << 20), what, ": n must be a multiple of 16 in "
+              "[16, 2^20], got ", n);
+  TORCH_CHECK(D == 32 || D == 64 || D == 128 || D == 256, what, ": D must be 32, 64, 128 or 256, "
+              "got ", D);
+}
+void check_nc_queue(const Tensor& queue, int64_t n, int64_t D, const char* what) {
+  TORCH_CHECK(queue.dim() == 2 && queue.size(1) == D, what, ": the queue must be [Q][", D,
+              "], got ", queue.sizes());
+  const int64_t Q = queue.size(0);
+  TORCH_CHECK(Q >= 256 && Q % 256 == 0 && Q <= (1 << 20) && n <= Q, what, ": Q must be a "
+              "multiple of 256 in [256, 2^20] and at least n = ", n, ", got ", Q);
+}
+// [2n][D] of the given dtype
+void check_nc_rows(const Tensor& t, int64_t n, int64_t D, const char* what, const char* name) {
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == 2 * n && t.size(1) == D, what, ": ", name,
+              " must be [", 2 * n, "][", D, "], got ", t.sizes());
+}
+int64_t nc_top1_splits(int64_t R, int64_t Q) {
+  TORCH_CHECK(R >= 32 && R % 32 == 0 && Q >= 256 && Q % 256 == 0 && Q <= (1 << 20),
+              "nc_top1_splits: R must be a multiple of 32 and Q a multiple of 256, got R ", R,
+              ", Q ", Q);
+  return nnclr_top1_splits((int)R, (int)Q);
+}
+int64_t nc_loss_splits(int64_t n) {
+  check_nc(n, 32, "nc_loss_splits");
+  return nnclr_loss_splits((int)n);
+}
+void nc_normalize(const Tensor& z, const Tensor& zn, const Tensor& zb, const Tensor& inv_norm) {
+  TORCH_CHECK(z.dim() == 2 && z.size(0) % 2 == 0, "nc_normalize: z must be [2n][D]");
+  const int64_t n = z.size(0) / 2, D = z.size(1);
+  check_nc(n, D, "nc_normalize");
+  TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
+                  (z.scalar_type() == at::kBFloat16 || z.scalar_type() == at::kFloat),
+              "nc_normalize: z must be a contiguous bf16 or fp32 GPU tensor");
+  check_nc_rows(zn, n, D, "nc_normalize", "zn");
+  check_nc_rows(zb, n, D, "nc_normalize", "zb");
+  TORCH_CHECK(inv_norm.numel() == 2 * n, "nc_normalize: inv_norm must hold 2n = ", 2 * n,
+              " values, got ", inv_norm.numel());
+  nnclr_normalize(z.data_ptr(), z.scalar_type() == at::kFloat ? 1 : 0, (int)(2 * n), (int)D,
+                  f32w(zn, "zn"), bfw(zb, "zb"), f32w(inv_norm, "inv_norm"), cur_stream());
+}
+void nc_lookup(const Tensor& zb, const Tensor& queue, int64_t splits, const Tensor& candv,
+               const Tensor& candi, const Tensor& idx, const Tensor& a) {
+  TORCH_CHECK(zb.dim() == 2 && zb.size(0) % 2 == 0, "nc_lookup: zb must be [2n][D]");
+  const int64_t n = zb.size(0) / 2, D = zb.size(1), R = 2 * n;
+  check_nc(n, D, "nc_lookup");
+  check_nc_queue(queue, n, D, "nc_lookup");
+  const int64_t Q = queue.size(0);
+  TORCH_CHECK(splits >= 1 && splits <= Q / 64, "nc_lookup: 1 <= splits <= Q / 64, got ", splits);
+  TORCH_CHECK(candv.numel() == splits * R && candi.numel() == splits * R,
+              "nc_lookup: candv / candi must be [splits][2n] = ", splits * R, " values, got ",
+              candv.numel(), " / ", candi.numel());
+  TORCH_CHECK(idx.numel() == R, "nc_lookup: idx must hold 2n = ", R, " values, got ", idx.numel());
+  check_nc_rows(a, n, D, "nc_lookup", "a");
+  check_dev(candi, at::kInt, "nc_lookup: candi");
+  check_dev(idx, at::kInt, "nc_lookup: idx");
+  nnclr_lookup(bf(zb, "zb"), bf(queue, "queue"), (int)R, (int)Q, (int)D, (int)splits,
+               f32w(candv, "candv"), candi.data_ptr<int>(), idx.data_ptr<int>(), bfw(a, "a"),
+               cur_stream());
+}
+void nc_forward(const Tensor& a, const Tensor& zb, double inv_temp, int64_t splits,
+                const Tensor& part) {
+  TORCH_CHECK(zb.dim() == 2 && zb.size(0) % 2 == 0, "nc_forward: zb must be [2n][D]");
+  const int64_t n = zb.size(0) / 2, D = zb.size(1);
+  check_nc(n, D, "nc_forward");
+  check_nc_rows(a, n, D, "nc_forward", "a");
+  TORCH_CHECK(splits >= 1 && splits <= n / 16 && part.numel() == splits * 2 * n * 3,
+              "nc_forward: part must be [splits][2n][3] with 1 <= splits <= n / 16, got splits ",
+              splits, ", ", part.numel(), " values");
+  TORCH_CHECK(inv_temp > 0.0, "nc_forward: the temperature must be > 0");
+  nnclr_forward(bf(a, "a"), bf(zb, "zb"), (int)n, (int)D, (float)inv_temp, (int)splits,
+                f32w(part, "part"), cur_stream());
+}
+void nc_backward(const Tensor& a, const Tensor& zb, const Tensor& zn, const Tensor& inv_norm,
+                 const Tensor& lse, double inv_temp, const Tensor& gout, int64_t splits,
+                 const Tensor& part, const c10::optional<Tensor>& dz_bf16,
+                 const c10::optional<Tensor>& dz_f32) {
+  TORCH_CHECK(zb.dim() == 2 && zb.size(0) % 2 == 0, "nc_backward: zb must be [2n][D]");
+  const int64_t n = zb.size(0) / 2, D = zb.size(1);
+  check_nc(n, D, "nc_backward");
+  check_nc_rows(a, n, D, "nc_backward", "a");
+  check_nc_rows(zn, n, D, "nc_backward", "zn");
+  TORCH_CHECK(inv_norm.numel() == 2 * n && lse.numel() == 2 * n && gout.numel() == 1,
+              "nc_backward: inv_norm and lse must hold 2n = ", 2 * n, " values and gout one");
+  TORCH_CHECK(splits >= 1 && splits <= n / 16 && part.numel() == splits * 2 * n * D,
+              "nc_backward: part must be [splits][2n][D] with 1 <= splits <= n / 16, got splits ",
+              splits, ", ", part.numel(), " values");
+  uint16_t* ob = optbfw(dz_bf16, "dz_bf16");
+  float* of = optf32w(dz_f32, "dz_f32");
+  TORCH_CHECK((ob != nullptr) != (of != nullptr), "nc_backward: one of dz_bf16 / dz_f32");
+  TORCH_CHECK((ob ? dz_bf16->numel() : dz_f32->numel()) == 2 * n * D, "nc_backward: dz size");
+  nnclr_backward(bf(a, "a"), bf(zb, "zb"), f32(zn, "zn"), f32(inv_norm, "inv_norm"),
+                 f32(lse, "lse"), (int)n, (int)D, (float)inv_temp, f32(gout, "gout"), (int)splits,
+                 f32w(part, "part"), ob, of, cur_stream());
+}
+void nc_enqueue(const Tensor& zb, const Tensor& queue, const Tensor& cursor) {
+  TORCH_CHECK(zb.dim() == 2 && zb.size(0) % 2 == 0, "nc_enqueue: zb must be [2n][D]");
+  const int64_t n = zb.size(0) / 2, D = zb.size(1);
+  check_nc(n, D, "nc_enqueue");
+  check_nc_queue(queue, n, D, "nc_enqueue");
+  check_dev(cursor, at::kInt, "nc_enqueue: cursor");
+  TORCH_CHECK(cursor.numel() == 1, "nc_enqueue: the cursor is one int32");
+  nnclr_enqueue(bf(zb, "zb"), (int)n, (int)D, (int)queue.size(0), bfw(queue, "queue"),
+                cursor.data_ptr<int>(), cur_stream());
+}
+
 // ------------------------------------------------------------------------------- barlow twins
 // (csrc/barlow.hip; every tensor's size is checked against n and D before any launch)
 void check_bt(int64_t n, int64_t D) {
@@ -1693,6 +1802,13 @@ TORCH_LIBRARY(simclr_amd, m) {
   m.def("nt_sup_finish(Tensor part, int R, int splits, Tensor(a!) lse, Tensor(b!) inv_cnt, Tensor(c!) loss) -> ()", &nt_sup_finish);
   m.def("nt_sup_backward_part(bool row_mode, Tensor zn, Tensor znT, Tensor lse, Tensor inv_cnt, Tensor ycol, int R, int col_offset, int n_local, float inv_temp, float gscale, Tensor? gout, Tensor(a!) part, int splits, Tensor(b!) out) -> ()", &nt_sup_backward_part);
   m.def("nt_expand_labels(Tensor labels, Tensor? idx, int views, Tensor(a!) out) -> ()", &nt_expand_labels);
+  m.def("nc_top1_splits(int R, int Q) -> int", &nc_top1_splits);
+  m.def("nc_loss_splits(int n) -> int", &nc_loss_splits);
+  m.def("nc_normalize(Tensor z, Tensor(a!) zn, Tensor(b!) zb, Tensor(c!) inv_norm) -> ()", &nc_normalize);
+  m.def("nc_lookup(Tensor zb, Tensor queue, int splits, Tensor(a!) candv, Tensor(b!) candi, Tensor(c!) idx, Tensor(d!) a) -> ()", &nc_lookup);
+  m.def("nc_forward(Tensor a, Tensor zb, float inv_temp, int splits, Tensor(a!) part) -> ()", &nc_forward);
+  m.def("nc_backward(Tensor a, Tensor zb, Tensor zn, Tensor inv_norm, Tensor lse, float inv_temp, Tensor gout, int splits, Tensor(a!) part, Tensor(b!)? dz_bf16, Tensor(c!)? dz_f32) -> ()", &nc_backward);
+  m.def("nc_enqueue(Tensor zb, Tensor(a!) queue, Tensor(b!) cursor) -> ()", &nc_enqueue);
   m.def("bt_standardize(Tensor z, float eps, Tensor(a!) rstd, Tensor(b!) zh, Tensor(c!) zhT) -> ()", &bt_standardize);
   m.def("bt_corr_splits(int n, int D) -> int", &bt_corr_splits);
   m.def("bt_loss_blocks(int D) -> int", &bt_loss_blocks);

@@ -274,6 +274,27 @@ void barlow_std_backward_global(const uint16_t* zh, const float* rstd, const flo
                                 const float* gsum, int W, int n, int D, uint16_t* dz_bf16,
                                 float* dz_f32, hipStream_t s);
 
+// ---- nnclr.hip  (NNCLR: nearest-neighbour lookup in a FIFO support set, cross-view InfoNCE)
+int nnclr_top1_splits(int R, int Q);  // queue splits of the lookup
+int nnclr_loss_splits(int n);         // column / anchor splits of the loss forward / backward
+// z [R][D] bf16 or fp32 -> zn fp32, zb bf16 (ẑ rounded once), inv_norm [R]
+void nnclr_normalize(const void* z, int z_f32, int R, int D, float* zn, uint16_t* zb,
+                     float* inv_norm, hipStream_t s);
+// idx[r] = argmax_k zb_r · Qm_k (similarity descending, index ascending), a[r] = Qm[idx[r]];
+// candv / candi [splits][R] scratch.  R % 32 == 0, Q % 64 == 0, D in {32, 64, 128, 256}
+void nnclr_lookup(const uint16_t* zb, const uint16_t* Qm, int R, int Q, int D, int splits,
+                  float* candv, int* candi, int* idx, uint16_t* a, hipStream_t s);
+// part [splits][2n][3] in ntxent_finish's format
+void nnclr_forward(const uint16_t* a, const uint16_t* zb, int n, int D, float inv_temp, int splits,
+                   float* part, hipStream_t s);
+// part [splits][2n][D] scratch; dz in bf16 or fp32 (one of the two)
+void nnclr_backward(const uint16_t* a, const uint16_t* zb, const float* zn, const float* inv_norm,
+                    const float* lse, int n, int D, float inv_temp, const float* gout, int splits,
+                    float* part, uint16_t* dz_bf16, float* dz_f32, hipStream_t s);
+// rows [0, n) of zb -> Qm[(cursor + b) mod Q], cursor <- (cursor + n) mod Q (one launch)
+void nnclr_enqueue(const uint16_t* zb, int n, int D, int Q, uint16_t* Qm, int* cursor,
+                   hipStream_t s);
+
 // ---- lars.hip (flat fp32 master / grad / momentum, bf16 shadow; per-segment table)
 void lars_norms(const float* p, const float* g, const int* chunk_beg, const int* chunk_end,
                 int nchunks, float grad_scale, float* norms, hipStream_t s);

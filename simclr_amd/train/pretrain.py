@@ -37,6 +37,7 @@ from ..config import check_pretrain_conf
 from ..data.datasets import load_dataset
 from ..data.loader import ContrastiveLoader, blur_kernel_from_cfg
 from ..loss.barlow import BarlowTwins
+from ..loss.nnclr import NNCLR
 from ..loss.ntxent import NTXent
 from ..models.contrastive import ContrastiveModel
 from ..ops import registry
@@ -96,7 +97,8 @@ class Trainer:
         self._early_updates()
         # loss.supervised: SupCon (loss/ntxent.py); step() / capture() then need the labels
         self.supervised = bool(cfg_get(cfg, "loss.supervised", False))
-        # loss.kind: ntxent (default) or barlow (Barlow Twins, loss/barlow.py: per rank, no labels)
+        # loss.kind: ntxent (default), barlow (Barlow Twins, loss/barlow.py: per rank, no labels)
+        # or nnclr (loss/nnclr.py: per rank, no labels, a support set of past embeddings)
         kind = cfg_get(cfg, "loss.kind", None) or "ntxent"
         if kind == "barlow":
             if self.supervised or cfg_get(cfg, "loss.gather", False) not in (None, False):
@@ -110,8 +112,21 @@ class Trainer:
             self.loss_fn = NTXent(temperature=cfg["parameter"]["temperature"],
                                   gather=cfg_get(cfg, "loss.gather", False),
                                   supervised=self.supervised)
+        elif kind == "nnclr":
+            # NNCLR (loss/nnclr.py): the support set and its cursor are built here, after the
+            # model, from a generator of their own, so no other initialisation depends on them
+            if (self.supervised or cfg_get(cfg, "loss.gather", False) not in (None, False)
+                    or cfg_get(cfg, "loss.barlow_global", False)):
+                raise ValueError("loss.kind=nnclr is not available with loss.supervised, "
+                                 "loss.gather or loss.barlow_global")
+            from ..config.validate import NN_QUEUE_DEFAULT
+            self.loss_fn = NNCLR(temperature=cfg["parameter"]["temperature"],
+                                 queue_size=cfg_get(cfg, "loss.nn_queue", None)
+                                 or NN_QUEUE_DEFAULT,
+                                 dim=cfg["parameter"]["d"], device=self.device,
+                                 seed=cfg["parameter"]["seed"])
         else:
-            raise ValueError(f"loss.kind must be ntxent or barlow, got {kind!r}")
+            raise ValueError(f"loss.kind must be ntxent, barlow or nnclr, got {kind!r}")
         # global negatives over RCCL: the fused head gathers z view by view under its GEMM 2
         # (models/head_fused.py _gemm2_pregather)
         zg = getattr(self.loss_fn, "gather", False) is True and bool(st.comm)
@@ -382,6 +397,12 @@ def pretrain(cfg) -> dict:
             else:
                 log.warning("resume file %s holds no online_probe entry: the online probe "
                             "starts fresh", resume)
+        if isinstance(tr.loss_fn, NNCLR):
+            if blob.get("nn_queue") is not None:
+                tr.loss_fn.load_queue_state(blob["nn_queue"])
+            else:
+                log.warning("resume file %s holds no nn_queue entry: the support set starts "
+                            "fresh", resume)
     max_steps = cfg_get(cfg, "runtime.max_steps", None)
     log_every = int(cfg_get(cfg, "runtime.log_every", 0) or 0)  # progress lines (syncs the step)
     graph_mode = _graph_mode(cfg_get(cfg, "runtime.hip_graph", "auto"))
@@ -483,7 +504,9 @@ def pretrain(cfg) -> dict:
                     save_resume("resume-{}.pt".format(epoch), tr.model, tr.opt, epoch,
                                 loader.counter, group=st.group if st.world_size > 1 else None,
                                 online_probe=(tr.probe.state_dict() if tr.probe is not None
-                                              else None))
+                                              else None),
+                                nn_queue=(tr.loss_fn.queue_state()
+                                          if isinstance(tr.loss_fn, NNCLR) else None))
         elif epoch % save_every == 0 and cfg_get(cfg, "runtime.save_resume", True):
             gather_rng_states(dst=0, group=st.group)  # rank 0's resume file holds every rank's
         if st.world_size > 1:

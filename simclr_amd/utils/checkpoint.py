@@ -95,15 +95,18 @@ def gather_rng_states(dst: int = 0, group=None) -> Optional[list]:
 
 def save_resume(path: str, model: nn.Module, optimizer, epoch: int, step: int,
                 extra: Optional[dict] = None, group=None,
-                online_probe: Optional[dict] = None) -> None:
+                online_probe: Optional[dict] = None, nn_queue: Optional[dict] = None) -> None:
     """Resume file (rank 0 writes it).  ``group``: multi-rank job — every other rank must call
     ``gather_rng_states(0, group)`` at the same point, so the file holds each rank's own
     generators (``rank_rng[r]``), restored per rank by ``restore_rng``.  ``online_probe``: the
     online probe's ``state_dict()`` (master, momentum, step), stored under that key; without
-    it the file has no such entry."""
+    it the file has no such entry.  ``nn_queue``: NNCLR's support set and cursor
+    (``NNCLR.queue_state()``), stored the same way."""
     local = _local_rng()
     ranks = gather_rng_states(0, group) if group is not None else [local]
     probe = {} if online_probe is None else {"online_probe": online_probe}
+    if nn_queue is not None:
+        probe["nn_queue"] = nn_queue
     torch.save({
         "model": reference_state_dict(model),
         "optimizer": optimizer.state_dict() if optimizer is not None else None,
