@@ -25,7 +25,7 @@ KERNEL_SOURCES = ["conv.hip", "bn.hip", "misc.hip", "ntxent.hip", "lars.hip", "a
                   "eval.hip", "comm.hip", "knn.hip", "probe.hip", "online_probe.hip",
                   "barlow.hip", "nnclr.hip"]
 BINDINGS = ["bindings.cpp", "ipc.cpp", "graphexec.cpp"]  # the units that see the ATen headers
-HEADERS = ["common.h", "kernels.h"]
+HEADERS = ["common.h", "contrast.h", "kernels.h"]
 ARCH = os.environ.get("SIMCLR_OFFLOAD_ARCH", "gfx950")
 
 

@@ -37,6 +37,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "contrast.h"
 #include "kernels.h"
 
 namespace {
@@ -228,23 +229,13 @@ __global__ __launch_bounds__(64) void k_nc_fwd(const uint16_t* __restrict__ a,
       const int c = q0 + 4 * g + i;
       const float x = s[i] * inv_temp;
       if (c == my_i) spos = x;
-      if (x > m) {
-        l = l * __expf(m - x) + 1.f;
-        m = x;
-      } else {
-        l += __expf(x - m);
-      }
+      lse_push(m, l, x);
     }
   }
 #pragma unroll
   for (int off = 16; off < 64; off <<= 1) {
-    const float m2 = __shfl_xor(m, off, 64);
-    const float l2 = __shfl_xor(l, off, 64);
-    const float p2 = __shfl_xor(spos, off, 64);
-    const float mn = fmaxf(m, m2);
-    l = (mn == -INFINITY) ? 0.f : l * __expf(m - mn) + l2 * __expf(m2 - mn);
-    m = mn;
-    spos = fmaxf(spos, p2);
+    lse_merge_lanes(m, l, off);
+    spos = fmaxf(spos, __shfl_xor(spos, off, 64));
   }
   if (g == 0) {
     float* dst = part + ((size_t)blockIdx.y * R + r0 + li) * 3;
@@ -400,15 +391,6 @@ void nnclr_normalize(const void* z, int z_f32, int R, int D, float* zn, uint16_t
   HIP_CHECK_LAUNCH();
 }
 
-#define NC_DISPATCH(D, CALL)                                              \
-  switch (D) {                                                            \
-    case 32: { constexpr int DD = 32; CALL; } break;                      \
-    case 64: { constexpr int DD = 64; CALL; } break;                      \
-    case 128: { constexpr int DD = 128; CALL; } break;                    \
-    case 256: { constexpr int DD = 256; CALL; } break;                    \
-    default: fprintf(stderr, "nnclr: unsupported D=%d\n", D); abort();    \
-  }
-
 void nnclr_lookup(const uint16_t* zb, const uint16_t* Qm, int R, int Q, int D, int splits,
                   float* candv, int* candi, int* idx, uint16_t* a, hipStream_t s) {
   if (!nc_dim_ok(D) || R % 32 || Q % 64 || splits < 1) {
@@ -417,8 +399,8 @@ void nnclr_lookup(const uint16_t* zb, const uint16_t* Qm, int R, int Q, int D, i
   }
   const int it = Q / 64;
   const int per = ((it + splits - 1) / splits) * 64;
-  NC_DISPATCH(D, hipLaunchKernelGGL(k_nc_top1<DD>, dim3(R / 32, splits), dim3(64), 0, s, zb, Qm, R,
-                                    Q, per, candv, candi));
+  DISPATCH_D(D, "nnclr", hipLaunchKernelGGL(k_nc_top1<DD>, dim3(R / 32, splits), dim3(64), 0, s,
+                                            zb, Qm, R, Q, per, candv, candi));
   HIP_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_nc_select, dim3((R + 3) / 4), dim3(256), 0, s, candv, candi, Qm, R, Q, D,
                      splits, idx, a);
@@ -433,8 +415,8 @@ void nnclr_forward(const uint16_t* a, const uint16_t* zb, int n, int D, float in
   }
   const int pt = n / 16;
   const int per = ((pt + splits - 1) / splits) * 16;
-  NC_DISPATCH(D, hipLaunchKernelGGL(k_nc_fwd<DD>, dim3(2 * n / 16, splits), dim3(64), 0, s, a, zb,
-                                    n, inv_temp, per, part));
+  DISPATCH_D(D, "nnclr", hipLaunchKernelGGL(k_nc_fwd<DD>, dim3(2 * n / 16, splits), dim3(64), 0,
+                                            s, a, zb, n, inv_temp, per, part));
   HIP_CHECK_LAUNCH();
 }
 
@@ -447,8 +429,8 @@ void nnclr_backward(const uint16_t* a, const uint16_t* zb, const float* zn, cons
   }
   const int R = 2 * n, pt = n / 16;
   const int per = ((pt + splits - 1) / splits) * 16;
-  NC_DISPATCH(D, hipLaunchKernelGGL(k_nc_bwd<DD>, dim3(R / 16, splits), dim3(64), 0, s, a, zb, lse,
-                                    n, inv_temp, gout, per, part));
+  DISPATCH_D(D, "nnclr", hipLaunchKernelGGL(k_nc_bwd<DD>, dim3(R / 16, splits), dim3(64), 0, s,
+                                            a, zb, lse, n, inv_temp, gout, per, part));
   HIP_CHECK_LAUNCH();
   hipLaunchKernelGGL(k_nc_norm_bwd, dim3((R + 3) / 4), dim3(256), 0, s, zn, inv_norm, part, splits,
                      R, D, dz_bf16, dz_f32);

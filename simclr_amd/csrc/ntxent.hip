@@ -19,6 +19,7 @@
 // Data: zn [Ccols][D] fp32 row-major and znT [D][Ccols] fp32 (both produced by the normalise /
 // transpose kernels), D % 4 == 0, D <= 256; R % 16 == 0, Ccols % 16 == 0.
 #include "common.h"
+#include "contrast.h"
 #include "kernels.h"
 
 namespace {
@@ -82,169 +83,22 @@ __device__ __forceinline__ f32x4_t sim_tile(const float* __restrict__ znT, int C
   return a0 + a1;
 }
 
-// Forward: grid (R/16, splits), one wave per block. Owned = anchor rows [r0, r0+16) (local),
-// partners = columns [c_beg, c_end). Writes part[split][r][3] = (max, sumexp, pos logit or -inf)
-template <int D>
-__global__ __launch_bounds__(64) void k_ntxent_fwd(const float* __restrict__ znT, int R, int Ccols,
-                                                   int col_offset, int n_local,
-                                                   float inv_temp, int cols_per_split,
-                                                   float* __restrict__ part, int c_lo, int c_hi,
-                                                   int split_base) {
-  const int lane = threadIdx.x;
-  const int g = lane >> 4, li = lane & 15;
-  const int r0 = blockIdx.x * 16;
-  const int split = split_base + blockIdx.y;
-  const int c_beg = c_lo + blockIdx.y * cols_per_split;
-  int c_end = c_beg + cols_per_split;
-  if (c_end > c_hi) c_end = c_hi;
-  float breg[D / 4];
-#pragma unroll
-  for (int ks = 0; ks < D / 4; ++ks)
-    breg[ks] = znT[(size_t)(4 * ks + g) * Ccols + col_offset + r0 + li];
-  const int my_r = r0 + li;  // owned row of this lane (o = li)
-  const int self_c = col_offset + my_r;
-  const int pos_c = pos_col(my_r, n_local, col_offset);
-  float m = -INFINITY, l = 0.f, spos = -INFINITY;
-  for (int q0 = c_beg; q0 < c_end; q0 += 16) {
-    const f32x4_t s = sim_tile<D>(znT, Ccols, q0, breg);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int c = q0 + 4 * g + i;
-      const float v = s[i] * inv_temp;
-      if (c == pos_c) spos = v;
-      if (c != self_c) {
-        if (v > m) {
-          l = l * __expf(m - v) + 1.f;
-          m = v;
-        } else {
-          l += __expf(v - m);
-        }
-      }
-    }
-  }
-  // merge across the 4 lane groups (g) holding the same row
-#pragma unroll
-  for (int off = 16; off < 64; off <<= 1) {
-    const float m2 = __shfl_xor(m, off, 64);
-    const float l2 = __shfl_xor(l, off, 64);
-    const float p2 = __shfl_xor(spos, off, 64);
-    const float mn = fmaxf(m, m2);
-    l = (mn == -INFINITY) ? 0.f : l * __expf(m - mn) + l2 * __expf(m2 - mn);
-    m = mn;
-    spos = fmaxf(spos, p2);
-  }
-  if (g == 0) {
-    float* dst = part + ((size_t)split * R + my_r) * 3;
-    dst[0] = m;
-    dst[1] = l;
-    dst[2] = spos;
-  }
-}
-
-// merge splits -> lse[r], loss[r]
-__global__ void k_ntxent_finish(const float* __restrict__ part, int R, int splits,
-                                float* __restrict__ lse, float* __restrict__ loss) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= R) return;
-  float m = -INFINITY, l = 0.f, sp = -INFINITY;
-  for (int s = 0; s < splits; ++s) {
-    const float* p = part + ((size_t)s * R + r) * 3;
-    const float mn = fmaxf(m, p[0]);
-    if (mn != -INFINITY) l = l * __expf(m - mn) + p[1] * __expf(p[0] - mn);
-    m = mn;
-    sp = fmaxf(sp, p[2]);
-  }
-  const float ls = m + logf(l);
-  lse[r] = ls;
-  loss[r] = ls - sp;
-}
-
-// Backward (owned/partner). ROW mode: owned = local anchor rows (lse by owned), partners =
-// columns. COL mode: owned = columns [o0..), partners = local anchor rows (lse by partner).
-// out[split][owned][D] += Σ_q w(q,o) ẑ_q ; w = gscale·(exp(s−lse_anchor) − [col==pos(anchor)])
-template <bool ROW, int D>
-__global__ __launch_bounds__(64) void k_ntxent_bwd(const float* __restrict__ zn,
-                                                   const float* __restrict__ znT,
-                                                   const float* __restrict__ lse, int R,
-                                                   int Ccols, int col_offset, int n_local,
-                                                   float inv_temp, float gscale,
-                                                   const float* __restrict__ gout,
-                                                   int partners_per_split,
-                                                   float* __restrict__ out) {
-  const int lane = threadIdx.x;
-  const int g = lane >> 4, li = lane & 15;
-  const int o0 = blockIdx.x * 16;  // ROW: local row index; COL: column index
-  const int split = blockIdx.y;
-  const int nown = ROW ? R : Ccols;
-  const int npart = ROW ? Ccols : R;
-  const int q_beg = split * partners_per_split;
-  int q_end = q_beg + partners_per_split;
-  if (q_end > npart) q_end = npart;
-  const float gs = gscale * (gout ? gout[0] : 1.f);
-  // owned operand (B of the similarity MFMA): column index in znT of owned item li
-  const int own_col = ROW ? (col_offset + o0 + li) : (o0 + li);
-  float breg[D / 4];
-#pragma unroll
-  for (int ks = 0; ks < D / 4; ++ks) breg[ks] = znT[(size_t)(4 * ks + g) * Ccols + own_col];
-  float lse_own = 0.f;
-  int self_c = -1, pos_c = -1;
-  if (ROW) {
-    const int r = o0 + li;
-    lse_own = lse[r];
-    self_c = col_offset + r;
-    pos_c = pos_col(r, n_local, col_offset);
-  }
-  constexpr int nd = D / 16;
-  f32x4_t acc[nd];
-#pragma unroll
-  for (int t = 0; t < nd; ++t) acc[t] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-  for (int q0 = q_beg; q0 < q_end; q0 += 16) {
-    const int qcol0 = ROW ? q0 : (col_offset + q0);  // partner column index in znT / zn
-    const f32x4_t s = sim_tile<D>(znT, Ccols, qcol0, breg);
-    float w[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float v = s[i] * inv_temp;
-      if (ROW) {
-        const int c = q0 + 4 * g + i;
-        const float p = (c == self_c) ? 0.f : __expf(v - lse_own);
-        w[i] = gs * (p - (c == pos_c ? 1.f : 0.f));
-      } else {
-        const int r = q0 + 4 * g + i;        // anchor (local row)
-        const int c = o0 + li;               // owned column
-        const float la = lse[r];
-        const int sc = col_offset + r;
-        const int pc = pos_col(r, n_local, col_offset);
-        const float p = (c == sc) ? 0.f : __expf(v - la);
-        w[i] = gs * (p - (c == pc ? 1.f : 0.f));
-      }
-    }
-    // acc[o][d] += Σ_q w(q,o) Z[q][d]: A[o=li][k=g] = w[t] (q = 4g+t), B[k=g][d=li] = Z[q][d]
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const float* zrow = zn + (size_t)(qcol0 + 4 * g + t) * D + li;
-#pragma unroll
-      for (int dt = 0; dt < nd; ++dt)
-        acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t], zrow[dt * 16], acc[dt], 0, 0, 0);
-    }
-  }
-  // lane holds out[o = 4g+i][d = dt*16 + li]
-  float* dst = out + (size_t)split * nown * D;
-#pragma unroll
-  for (int dt = 0; dt < nd; ++dt)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      dst[(size_t)(o0 + 4 * g + i) * D + dt * 16 + li] = acc[dt][i] * inv_temp;
-}
-
-// ---------------------------------------------------------------- label mode (SupCon)
-// The supervised contrastive loss: the positives of anchor i are every column but its own with
-// the anchor's label, loss_i = LSE_{a≠i} s_ia − (1/|P(i)|) Σ_{p∈P(i)} s_ip.  The kernels below
-// are the NT-Xent ones with the positive test "c == pos_col" replaced by a label compare; they
-// are separate kernels so that the unlabelled ones keep their code.  Labels: ycol[Ccols] int32,
-// one per column (view-expanded, rank-major as the columns).  With all labels distinct the
-// arithmetic is that of NT-Xent operation for operation (one match: the positive sum is that
-// one value plus zeros, the count 1.0f, 1/count 1.0f).
+// ---------------------------------------------------------------- positive rules
+// Which columns are an anchor's positives is a compile-time "positive rule"; the forward, finish
+// and backward kernels below are written once over it.
+//   pair  (NT-Xent): the other view of the anchor's image, pos_col.  Forward partial
+//         part[split][r][3] = (max, sumexp, positive logit or -inf); backward weight 1.
+//   label (SupCon):  every column but the anchor's own with the anchor's label,
+//         loss_i = LSE_{a≠i} s_ia − (1/|P(i)|) Σ_{p∈P(i)} s_ip.  Labels: ycol int32, one per
+//         column (view-expanded, rank-major as the columns).  Forward partial
+//         part[split][r][4] = (max, sumexp, Σ s over matches, count of matches); backward weight
+//         1/|P(anchor)|.
+// What the template guarantees: a rule is resolved when the kernel is instantiated, so the pair
+// kernels hold no label load, compare or pointer read, and every instantiation runs the same
+// online log-sum-exp (contrast.h), the same similarity tiles and the same merge order over lane
+// groups and then splits.  With all labels distinct the label rule's arithmetic is therefore
+// that of the pair rule operation for operation (one match: the positive sum is that one value
+// plus zeros, the count 1.0f, 1/count 1.0f), and the two losses agree bit for bit.
 
 // labels of the four consecutive items [i, i + 4), i % 4 == 0; one 16-byte load if VEC (the
 // host picks VEC = the array is 16-byte aligned; compile-time, so the tile loop stays free of
@@ -260,16 +114,80 @@ __device__ __forceinline__ void load_labels4(const int* __restrict__ y, int i, i
   }
 }
 
-// Forward as k_ntxent_fwd; ycol holds the labels of columns [y0, y0 + len) (the window and the
-// owned rows lie inside).  Writes part[split][r][4] = (max, sumexp, Σ s over matches, count of
-// matches), self excluded.
-template <int D, bool VEC>
-__global__ __launch_bounds__(64) void k_supcon_fwd(const float* __restrict__ znT,
-                                                   const int* __restrict__ ycol, int y0,
-                                                   int R, int Ccols, int col_offset,
-                                                   float inv_temp, int cols_per_split,
-                                                   float* __restrict__ part, int c_lo, int c_hi,
-                                                   int split_base) {
+// the positive of a row: one logit; lane groups and splits merge by max (-inf where absent)
+struct PairPos {
+  static constexpr int NP = 3;  // floats per row of a forward partial
+  float s = -INFINITY;
+  __device__ __forceinline__ void add(float v) { s = v; }
+  __device__ __forceinline__ void merge_lanes(int off) { s = fmaxf(s, __shfl_xor(s, off, 64)); }
+  __device__ __forceinline__ void merge_split(const float* p) { s = fmaxf(s, p[0]); }
+  __device__ __forceinline__ void store(float* p) const { p[0] = s; }
+  __device__ __forceinline__ float term(float*, int) const { return s; }
+};
+
+// the positives of a row: sum and count, merged by + in lane-group and then split order
+struct LabelPos {
+  static constexpr int NP = 4;
+  float sum = 0.f, cnt = 0.f;
+  __device__ __forceinline__ void add(float v) { sum += v, cnt += 1.f; }
+  __device__ __forceinline__ void merge_lanes(int off) {
+    sum += __shfl_xor(sum, off, 64);
+    cnt += __shfl_xor(cnt, off, 64);
+  }
+  __device__ __forceinline__ void merge_split(const float* p) { sum += p[0], cnt += p[1]; }
+  __device__ __forceinline__ void store(float* p) const { p[0] = sum, p[1] = cnt; }
+  // mean positive logit; 1/|P| is kept for the backward
+  __device__ __forceinline__ float term(float* inv_cnt, int r) const {
+    const float ic = 1.f / cnt;
+    inv_cnt[r] = ic;
+    return sum * ic;
+  }
+};
+
+// A rule is built per lane from the kernel's arguments and the lane's owned column own_c; r is
+// an anchor (local row), c a column, i the partner's place in the lane's four of the tile.
+struct PairRule {
+  using Pos = PairPos;
+  const int n_local, col_offset;
+  __device__ __forceinline__ PairRule(const int*, int, const float*, int n_local, int col_offset,
+                                      int)
+      : n_local(n_local), col_offset(col_offset) {}
+  __device__ __forceinline__ void load_tile(int) {}
+  __device__ __forceinline__ bool is_pos(int r, int c, bool, int) const {
+    return c == pos_col(r, n_local, col_offset);
+  }
+  __device__ __forceinline__ float pos_weight(int) const { return 1.f; }
+};
+
+// ycol holds the labels of the columns [y0, ...); inv_cnt (backward) 1/|P| per local row
+template <bool VEC>
+struct LabelRule {
+  using Pos = LabelPos;
+  const int* __restrict__ const ycol;
+  const float* __restrict__ const inv_cnt;
+  const int y0, y_own;
+  int yl[4];
+  __device__ __forceinline__ LabelRule(const int* __restrict__ ycol, int y0,
+                                       const float* __restrict__ inv_cnt, int, int, int own_c)
+      : ycol(ycol), inv_cnt(inv_cnt), y0(y0), y_own(ycol[own_c - y0]) {}
+  // the labels of the partner columns [c, c + 4)
+  __device__ __forceinline__ void load_tile(int c) { load_labels4<VEC>(ycol, c - y0, yl); }
+  __device__ __forceinline__ bool is_pos(int, int, bool self, int i) const {
+    return !self & (yl[i] == y_own);
+  }
+  __device__ __forceinline__ float pos_weight(int r) const { return inv_cnt[r]; }
+};
+
+// Forward: grid (R/16, splits), one wave per block. Owned = anchor rows [r0, r0+16) (local),
+// partners = columns [c_beg, c_end). Writes part[split][r][Pos::NP], self excluded.  ycol / y0
+// are the label rule's (the window and the owned rows lie inside), n_local the pair rule's.
+template <int D, class Rule>
+__global__ __launch_bounds__(64) void k_ntxent_fwd(const float* __restrict__ znT,
+                                                     int R, int Ccols, int col_offset,
+                                                     int n_local, float inv_temp,
+                                                     int cols_per_split, float* __restrict__ part,
+                                                     int c_lo, int c_hi, int split_base,
+                                                     const int* __restrict__ ycol, int y0) {
   const int lane = threadIdx.x;
   const int g = lane >> 4, li = lane & 15;
   const int r0 = blockIdx.x * 16;
@@ -283,84 +201,69 @@ __global__ __launch_bounds__(64) void k_supcon_fwd(const float* __restrict__ znT
     breg[ks] = znT[(size_t)(4 * ks + g) * Ccols + col_offset + r0 + li];
   const int my_r = r0 + li;  // owned row of this lane (o = li)
   const int self_c = col_offset + my_r;
-  const int y_own = ycol[self_c - y0];
-  float m = -INFINITY, l = 0.f, psum = 0.f, pcnt = 0.f;
+  Rule rule(ycol, y0, nullptr, n_local, col_offset, self_c);
+  typename Rule::Pos pos;
+  float m = -INFINITY, l = 0.f;
   for (int q0 = c_beg; q0 < c_end; q0 += 16) {
     const f32x4_t s = sim_tile<D>(znT, Ccols, q0, breg);
-    int yl[4];
-    load_labels4<VEC>(ycol, q0 + 4 * g - y0, yl);
+    rule.load_tile(q0 + 4 * g);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int c = q0 + 4 * g + i;
       const float v = s[i] * inv_temp;
-      if (c != self_c) {
-        if (v > m) {
-          l = l * __expf(m - v) + 1.f;
-          m = v;
-        } else {
-          l += __expf(v - m);
-        }
-        if (yl[i] == y_own) {
-          psum += v;
-          pcnt += 1.f;
-        }
-      }
+      const bool self = c == self_c;
+      if (rule.is_pos(my_r, c, self, i)) pos.add(v);
+      if (!self) lse_push(m, l, v);
     }
   }
   // merge across the 4 lane groups (g) holding the same row
 #pragma unroll
   for (int off = 16; off < 64; off <<= 1) {
-    const float m2 = __shfl_xor(m, off, 64);
-    const float l2 = __shfl_xor(l, off, 64);
-    const float mn = fmaxf(m, m2);
-    l = (mn == -INFINITY) ? 0.f : l * __expf(m - mn) + l2 * __expf(m2 - mn);
-    m = mn;
-    psum += __shfl_xor(psum, off, 64);
-    pcnt += __shfl_xor(pcnt, off, 64);
+    lse_merge_lanes(m, l, off);
+    pos.merge_lanes(off);
   }
   if (g == 0) {
-    float* dst = part + ((size_t)split * R + my_r) * 4;
+    float* dst = part + ((size_t)split * R + my_r) * Rule::Pos::NP;
     dst[0] = m;
     dst[1] = l;
-    dst[2] = psum;
-    dst[3] = pcnt;
+    pos.store(dst + 2);
   }
 }
 
-// merge splits in order -> lse[r], inv_cnt[r] = 1/|P(r)|, loss[r]
-__global__ void k_supcon_finish(const float* __restrict__ part, int R, int splits,
-                                float* __restrict__ lse, float* __restrict__ inv_cnt,
-                                float* __restrict__ loss) {
+// merge splits in order -> lse[r], loss[r] (and the label rule's inv_cnt[r] = 1/|P(r)|)
+template <class Pos>
+__global__ void k_ntxent_finish(const float* __restrict__ part, int R, int splits,
+                                  float* __restrict__ lse, float* __restrict__ inv_cnt,
+                                  float* __restrict__ loss) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
-  float m = -INFINITY, l = 0.f, ps = 0.f, pc = 0.f;
+  float m = -INFINITY, l = 0.f;
+  Pos pos;
   for (int s = 0; s < splits; ++s) {
-    const float* p = part + ((size_t)s * R + r) * 4;
-    const float mn = fmaxf(m, p[0]);
-    if (mn != -INFINITY) l = l * __expf(m - mn) + p[1] * __expf(p[0] - mn);
-    m = mn;
-    ps += p[2];
-    pc += p[3];
+    const float* p = part + ((size_t)s * R + r) * Pos::NP;
+    lse_merge_split(m, l, p);
+    pos.merge_split(p + 2);
   }
   const float ls = m + logf(l);
-  const float ic = 1.f / pc;
   lse[r] = ls;
-  inv_cnt[r] = ic;
-  loss[r] = ls - ps * ic;
+  loss[r] = ls - pos.term(inv_cnt, r);
 }
 
-// Backward as k_ntxent_bwd with w = gscale·(exp(s−lse_anchor) − [col∈P(anchor)]/|P(anchor)|);
-// ycol covers every column (base 0).
-template <bool ROW, int D, bool VEC>
-__global__ __launch_bounds__(64) void k_supcon_bwd(const float* __restrict__ zn,
-                                                   const float* __restrict__ znT,
-                                                   const float* __restrict__ lse,
-                                                   const float* __restrict__ inv_cnt,
-                                                   const int* __restrict__ ycol, int R,
-                                                   int Ccols, int col_offset, float inv_temp,
-                                                   float gscale, const float* __restrict__ gout,
-                                                   int partners_per_split,
-                                                   float* __restrict__ out) {
+// Backward (owned/partner). ROW mode: owned = local anchor rows (lse by owned), partners =
+// columns. COL mode: owned = columns [o0..), partners = local anchor rows (lse by partner).
+// out[split][owned][D] += Σ_q w(q,o) ẑ_q ;
+// w = gscale·(exp(s−lse_anchor) − [col∈P(anchor)]·pos_weight(anchor)); ycol covers every column
+template <bool ROW, int D, class Rule>
+__global__ __launch_bounds__(64) void k_ntxent_bwd(const float* __restrict__ zn,
+                                                     const float* __restrict__ znT,
+                                                     const float* __restrict__ lse, int R,
+                                                     int Ccols, int col_offset, int n_local,
+                                                     float inv_temp, float gscale,
+                                                     const float* __restrict__ gout,
+                                                     int partners_per_split,
+                                                     float* __restrict__ out,
+                                                     const float* __restrict__ inv_cnt,
+                                                     const int* __restrict__ ycol) {
   const int lane = threadIdx.x;
   const int g = lane >> 4, li = lane & 15;
   const int o0 = blockIdx.x * 16;  // ROW: local row index; COL: column index
@@ -371,15 +274,16 @@ __global__ __launch_bounds__(64) void k_supcon_bwd(const float* __restrict__ zn,
   int q_end = q_beg + partners_per_split;
   if (q_end > npart) q_end = npart;
   const float gs = gscale * (gout ? gout[0] : 1.f);
+  // owned operand (B of the similarity MFMA): column index in znT of owned item li
   const int own_col = ROW ? (col_offset + o0 + li) : (o0 + li);
   float breg[D / 4];
 #pragma unroll
   for (int ks = 0; ks < D / 4; ++ks) breg[ks] = znT[(size_t)(4 * ks + g) * Ccols + own_col];
-  const int y_own = ycol[own_col];
-  float lse_own = 0.f, ic_own = 0.f;
+  Rule rule(ycol, 0, inv_cnt, n_local, col_offset, own_col);
+  float lse_own = 0.f, pw_own = 0.f;
   if (ROW) {
     lse_own = lse[o0 + li];
-    ic_own = inv_cnt[o0 + li];
+    pw_own = rule.pos_weight(o0 + li);
   }
   constexpr int nd = D / 16;
   f32x4_t acc[nd];
@@ -388,24 +292,20 @@ __global__ __launch_bounds__(64) void k_supcon_bwd(const float* __restrict__ zn,
   for (int q0 = q_beg; q0 < q_end; q0 += 16) {
     const int qcol0 = ROW ? q0 : (col_offset + q0);  // partner column index in znT / zn
     const f32x4_t s = sim_tile<D>(znT, Ccols, qcol0, breg);
-    int yl[4];  // the partners' labels (ROW: columns; COL: anchors, as columns of this rank)
-    load_labels4<VEC>(ycol, qcol0 + 4 * g, yl);
+    rule.load_tile(qcol0 + 4 * g);  // (ROW: columns; COL: anchors, as columns of this rank)
     float w[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const float v = s[i] * inv_temp;
-      if (ROW) {
-        const int c = q0 + 4 * g + i;
-        const bool self = c == own_col;
-        const float p = self ? 0.f : __expf(v - lse_own);
-        w[i] = gs * (p - ((!self && yl[i] == y_own) ? ic_own : 0.f));
-      } else {
-        const int r = q0 + 4 * g + i;  // anchor (local row)
-        const bool self = own_col == col_offset + r;
-        const float p = self ? 0.f : __expf(v - lse[r]);
-        w[i] = gs * (p - ((!self && yl[i] == y_own) ? inv_cnt[r] : 0.f));
-      }
+      const int r = ROW ? o0 + li : q0 + 4 * g + i;  // anchor (local row)
+      const int c = ROW ? q0 + 4 * g + i : o0 + li;  // column
+      const float la = ROW ? lse_own : lse[r];
+      const bool self = c == col_offset + r;
+      const bool pos = rule.is_pos(r, c, self, i);
+      const float p = self ? 0.f : __expf(v - la);
+      w[i] = gs * (p - (pos ? (ROW ? pw_own : rule.pos_weight(r)) : 0.f));
     }
+    // acc[o][d] += Σ_q w(q,o) Z[q][d]: A[o=li][k=g] = w[t] (q = 4g+t), B[k=g][d=li] = Z[q][d]
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
       const float* zrow = zn + (size_t)(qcol0 + 4 * g + t) * D + li;
@@ -414,6 +314,7 @@ __global__ __launch_bounds__(64) void k_supcon_bwd(const float* __restrict__ zn,
         acc[dt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[t], zrow[dt * 16], acc[dt], 0, 0, 0);
     }
   }
+  // lane holds out[o = 4g+i][d = dt*16 + li]
   float* dst = out + (size_t)split * nown * D;
 #pragma unroll
   for (int dt = 0; dt < nd; ++dt)
@@ -523,28 +424,61 @@ int ntxent_bwd_splits(int nown, int npart) {
   return splits_for(nown / 16, npart / 16, nown <= npart ? 8 : 16);
 }
 
+static bool labels_vec(const int* y) { return ((uintptr_t)y & 15) == 0; }
+
+// Runs the statement(s) with RULE = the positive rule: the label rule if there are labels (its
+// 16-byte loads if they are aligned), else the pair rule.
+#define DISPATCH_RULE(ycol, ...)                                            \
+  if (!(ycol)) { using RULE = PairRule; __VA_ARGS__; }                      \
+  else if (labels_vec(ycol)) { using RULE = LabelRule<true>; __VA_ARGS__; } \
+  else { using RULE = LabelRule<false>; __VA_ARGS__; }
+
 // columns [c_lo, c_hi) of znT into splits [split_base, split_base + splits) of part
-void ntxent_forward_range(const float* znT, int R, int Ccols, int D, int col_offset, int n_local,
-                          float inv_temp, float* part, int c_lo, int c_hi, int splits,
-                          int split_base, hipStream_t s) {
+// (y0 % 16 == 0: the tile offsets keep the labels' alignment)
+static void forward_range(const float* znT, const int* ycol, int y0, int R, int Ccols, int D,
+                          int col_offset, int n_local, float inv_temp, float* part, int c_lo,
+                          int c_hi, int splits, int split_base, hipStream_t s) {
   const int ptiles = (c_hi - c_lo) / 16;
   const int per = ((ptiles + splits - 1) / splits) * 16;
-#define FWD_CASE(DD)                                                                        \
-  case DD:                                                                                  \
-    hipLaunchKernelGGL(k_ntxent_fwd<DD>, dim3(R / 16, splits), dim3(64), 0, s, znT, R, Ccols, \
-                       col_offset, n_local, inv_temp, per, part, c_lo, c_hi, split_base);   \
-    break;
-  switch (D) {
-    FWD_CASE(32) FWD_CASE(64) FWD_CASE(128) FWD_CASE(256)
-    default: fprintf(stderr, "ntxent: unsupported D=%d\n", D); abort();
-  }
-#undef FWD_CASE
+  DISPATCH_D(D, "ntxent", DISPATCH_RULE(ycol, hipLaunchKernelGGL(
+      (k_ntxent_fwd<DD, RULE>), dim3(R / 16, splits), dim3(64), 0, s, znT, R, Ccols, col_offset,
+      n_local, inv_temp, per, part, c_lo, c_hi, split_base, ycol, y0)));
   HIP_CHECK_LAUNCH();
 }
 
+static void backward_part(int row_mode, const float* zn, const float* znT, const float* lse,
+                          const float* inv_cnt, const int* ycol, int R, int Ccols, int D,
+                          int col_offset, int n_local, float inv_temp, float gscale,
+                          const float* gout, float* part, int splits, float* out, hipStream_t s) {
+  const int nown = row_mode ? R : Ccols;
+  const int npart = row_mode ? Ccols : R;
+  const int ptiles = npart / 16;
+  const int per = ((ptiles + splits - 1) / splits) * 16;
+#define BWD_LAUNCH(ROW)                                                                         \
+  hipLaunchKernelGGL((k_ntxent_bwd<ROW, DD, RULE>), dim3(nown / 16, splits), dim3(64), 0, s,  \
+                     zn, znT, lse, R, Ccols, col_offset, n_local, inv_temp, gscale, gout, per,  \
+                     part, inv_cnt, ycol)
+  DISPATCH_D(D, "ntxent", DISPATCH_RULE(ycol, if (row_mode) BWD_LAUNCH(true);
+                                        else BWD_LAUNCH(false)));
+#undef BWD_LAUNCH
+  HIP_CHECK_LAUNCH();
+  const size_t n = (size_t)nown * D;
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(k_sum_splits, dim3(blocks), dim3(256), 0, s, part, splits, n, out);
+  HIP_CHECK_LAUNCH();
+}
+
+void ntxent_forward_range(const float* znT, int R, int Ccols, int D, int col_offset, int n_local,
+                          float inv_temp, float* part, int c_lo, int c_hi, int splits,
+                          int split_base, hipStream_t s) {
+  forward_range(znT, nullptr, 0, R, Ccols, D, col_offset, n_local, inv_temp, part, c_lo, c_hi,
+                splits, split_base, s);
+}
+
 void ntxent_finish(const float* part, int R, int splits, float* lse, float* loss, hipStream_t s) {
-  hipLaunchKernelGGL(k_ntxent_finish, dim3((R + 255) / 256), dim3(256), 0, s, part, R, splits, lse,
-                     loss);
+  hipLaunchKernelGGL(k_ntxent_finish<PairPos>, dim3((R + 255) / 256), dim3(256), 0, s, part, R,
+                     splits, lse, nullptr, loss);
   HIP_CHECK_LAUNCH();
 }
 
@@ -560,64 +494,23 @@ void ntxent_backward_part(int row_mode, const float* zn, const float* znT, const
                           int Ccols, int D, int col_offset, int n_local, float inv_temp,
                           float gscale, const float* gout, float* part, int splits, float* out,
                           hipStream_t s) {
-  const int nown = row_mode ? R : Ccols;
-  const int npart = row_mode ? Ccols : R;
-  const int ptiles = npart / 16;
-  const int per = ((ptiles + splits - 1) / splits) * 16;
-#define BWD_CASE(DD)                                                                          \
-  case DD:                                                                                    \
-    if (row_mode)                                                                             \
-      hipLaunchKernelGGL((k_ntxent_bwd<true, DD>), dim3(nown / 16, splits), dim3(64), 0, s, zn, \
-                         znT, lse, R, Ccols, col_offset, n_local, inv_temp, gscale, gout, per,  \
-                         part);                                                               \
-    else                                                                                      \
-      hipLaunchKernelGGL((k_ntxent_bwd<false, DD>), dim3(nown / 16, splits), dim3(64), 0, s,    \
-                         zn, znT, lse, R, Ccols, col_offset, n_local, inv_temp, gscale, gout,   \
-                         per, part);                                                          \
-    break;
-  switch (D) {
-    BWD_CASE(32) BWD_CASE(64) BWD_CASE(128) BWD_CASE(256)
-    default: fprintf(stderr, "ntxent: unsupported D=%d\n", D); abort();
-  }
-#undef BWD_CASE
-  HIP_CHECK_LAUNCH();
-  const size_t n = (size_t)nown * D;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_sum_splits, dim3(blocks), dim3(256), 0, s, part, splits, n, out);
-  HIP_CHECK_LAUNCH();
+  backward_part(row_mode, zn, znT, lse, nullptr, nullptr, R, Ccols, D, col_offset, n_local,
+                inv_temp, gscale, gout, part, splits, out, s);
 }
 
-// ---- label mode (SupCon)
-static bool labels_vec(const int* y) { return ((uintptr_t)y & 15) == 0; }
-
+// ---- label mode (SupCon): ycol must not be null (the pair rule needs n_local, which these
+// do not take)
 void supcon_forward_range(const float* znT, const int* ycol, int y0, int R, int Ccols, int D,
                           int col_offset, float inv_temp, float* part, int c_lo, int c_hi,
                           int splits, int split_base, hipStream_t s) {
-  const int ptiles = (c_hi - c_lo) / 16;
-  const int per = ((ptiles + splits - 1) / splits) * 16;
-  const bool yvec = labels_vec(ycol);  // (y0 % 16 == 0: the tile offsets keep the alignment)
-#define FWD_LAUNCH(DD, VV)                                                                    \
-  hipLaunchKernelGGL((k_supcon_fwd<DD, VV>), dim3(R / 16, splits), dim3(64), 0, s, znT, ycol, \
-                     y0, R, Ccols, col_offset, inv_temp, per, part, c_lo, c_hi, split_base)
-#define FWD_CASE(DD)                \
-  case DD:                          \
-    if (yvec) FWD_LAUNCH(DD, true); \
-    else FWD_LAUNCH(DD, false);     \
-    break;
-  switch (D) {
-    FWD_CASE(32) FWD_CASE(64) FWD_CASE(128) FWD_CASE(256)
-    default: fprintf(stderr, "supcon: unsupported D=%d\n", D); abort();
-  }
-#undef FWD_CASE
-#undef FWD_LAUNCH
-  HIP_CHECK_LAUNCH();
+  forward_range(znT, ycol, y0, R, Ccols, D, col_offset, 0, inv_temp, part, c_lo, c_hi, splits,
+                split_base, s);
 }
 
 void supcon_finish(const float* part, int R, int splits, float* lse, float* inv_cnt, float* loss,
                    hipStream_t s) {
-  hipLaunchKernelGGL(k_supcon_finish, dim3((R + 255) / 256), dim3(256), 0, s, part, R, splits, lse,
-                     inv_cnt, loss);
+  hipLaunchKernelGGL(k_ntxent_finish<LabelPos>, dim3((R + 255) / 256), dim3(256), 0, s, part, R,
+                     splits, lse, inv_cnt, loss);
   HIP_CHECK_LAUNCH();
 }
 
@@ -625,34 +518,8 @@ void supcon_backward_part(int row_mode, const float* zn, const float* znT, const
                           const float* inv_cnt, const int* ycol, int R, int Ccols, int D,
                           int col_offset, float inv_temp, float gscale, const float* gout,
                           float* part, int splits, float* out, hipStream_t s) {
-  const int nown = row_mode ? R : Ccols;
-  const int npart = row_mode ? Ccols : R;
-  const int ptiles = npart / 16;
-  const int per = ((ptiles + splits - 1) / splits) * 16;
-  const bool yvec = labels_vec(ycol);
-#define BWD_LAUNCH(RR, DD, VV)                                                                 \
-  hipLaunchKernelGGL((k_supcon_bwd<RR, DD, VV>), dim3(nown / 16, splits), dim3(64), 0, s, zn,  \
-                     znT, lse, inv_cnt, ycol, R, Ccols, col_offset, inv_temp, gscale, gout,    \
-                     per, part)
-#define BWD_CASE(DD)                                   \
-  case DD:                                             \
-    if (row_mode && yvec) BWD_LAUNCH(true, DD, true);  \
-    else if (row_mode) BWD_LAUNCH(true, DD, false);    \
-    else if (yvec) BWD_LAUNCH(false, DD, true);        \
-    else BWD_LAUNCH(false, DD, false);                 \
-    break;
-  switch (D) {
-    BWD_CASE(32) BWD_CASE(64) BWD_CASE(128) BWD_CASE(256)
-    default: fprintf(stderr, "supcon: unsupported D=%d\n", D); abort();
-  }
-#undef BWD_CASE
-#undef BWD_LAUNCH
-  HIP_CHECK_LAUNCH();
-  const size_t n = (size_t)nown * D;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_sum_splits, dim3(blocks), dim3(256), 0, s, part, splits, n, out);
-  HIP_CHECK_LAUNCH();
+  backward_part(row_mode, zn, znT, lse, inv_cnt, ycol, R, Ccols, D, col_offset, 0, inv_temp,
+                gscale, gout, part, splits, out, s);
 }
 
 void supcon_expand_labels(const void* labels, int labels_i64, const int64_t* idx, long n_src,

@@ -155,16 +155,44 @@ def take_pregather(z: torch.Tensor):
 
 
 class _NTXentHipFn(torch.autograd.Function):
+    """NT-Xent (``y`` None) or, with the labels ``y[n]``, SupCon on the label-mode kernels
+    (``nt_sup_*``): the rank's view-expanded int32 label block is built on the device
+    (``nt_expand_labels``) and, for the gathered loss, all-gathered on the side stream right
+    behind z.  The order of the ``torch.empty`` calls, launches, collectives and stream waits
+    of each mode is part of the contract: the step is captured into a graph and replayed."""
+
     @staticmethod
-    def forward(ctx, z, n, temperature, reduction, gather, st):
+    def forward(ctx, z, y, n, temperature, reduction, gather, st):
         from ..ops import _ext
         ops = _ext.ops()
         R, D = z.shape
         dev = z.device
         zb = z.contiguous() if z.dtype == torch.bfloat16 else z.to(torch.bfloat16).contiguous()
         inv_t = 1.0 / temperature
+        labelled = y is not None
+        npart = 4 if labelled else 3  # floats per row of a forward partial
         lse = torch.empty((R,), device=dev, dtype=torch.float32)
+        inv_cnt = torch.empty((R,), device=dev, dtype=torch.float32) if labelled else None
         rows = torch.empty((R,), device=dev, dtype=torch.float32)
+        y_loc = ycol = None
+        if labelled:
+            y_loc = torch.empty((R,), device=dev, dtype=torch.int32)
+            ops.nt_expand_labels(y, None, 2, y_loc)
+
+        def score(labels, y0, lo, hi, splits, base):
+            # columns [lo, hi) into the partials [base, base + splits); labels cover [y0, ...)
+            if labelled:
+                ops.nt_sup_forward_range(znT, labels, y0, R, col_offset, n, inv_t, part, lo, hi,
+                                         splits, base)
+            else:
+                ops.nt_forward_range(znT, R, col_offset, n, inv_t, part, lo, hi, splits, base)
+
+        def finish(splits):
+            if labelled:
+                ops.nt_sup_finish(part, R, splits, lse, inv_cnt, rows)
+            else:
+                ops.nt_finish(part, R, splits, lse, rows)
+
         if gather and st.comm:
             # global negatives: the ranks exchange bf16 z (half the bytes of gathering fp32 ẑ) on
             # a side stream.  Meanwhile this rank normalises its own rows and scores them against
@@ -179,6 +207,9 @@ class _NTXentHipFn(torch.autograd.Function):
             side = _side_stream(dev)
             side.wait_stream(cur)
             pre = take_pregather(zb)
+            ipc = getattr(st, "ipc", None)  # one-shot stores over xGMI (comm/ipc.py, csrc/comm.hip)
+            if labelled:
+                ycol = torch.empty((Ccols,), device=dev, dtype=torch.int32)
             if pre is not None and tuple(pre[0].shape) == (Ccols, D):
                 # the head gathered z view by view on this side stream, under its GEMM 2
                 zb_all, pre_keep = pre
@@ -186,11 +217,16 @@ class _NTXentHipFn(torch.autograd.Function):
                 pre_keep = pre  # (a mismatched pre-gather's buffers: still in use on the side stream)
                 zb_all = torch.empty((Ccols, D), device=dev, dtype=torch.bfloat16)
                 with torch.cuda.stream(side):
-                    ipc = getattr(st, "ipc", None)
-                    if ipc is not None:  # one-shot stores over xGMI (comm/ipc.py, csrc/comm.hip)
+                    if ipc is not None:
                         ipc.all_gather(("ntxent", "z"), zb, zb_all)
                     else:
                         dist.all_gather_into_tensor(zb_all, zb, group=st.group)
+            if labelled:
+                with torch.cuda.stream(side):  # the labels: one more small collective, same wait
+                    if ipc is not None:
+                        ipc.all_gather(("ntxent", "y"), y_loc, ycol)
+                    else:
+                        dist.all_gather_into_tensor(ycol, y_loc, group=st.group)
             zall = torch.empty((Ccols, D), device=dev, dtype=torch.float32)
             inv_all = torch.empty((Ccols,), device=dev, dtype=torch.float32)
             zn = zall[col_offset:col_offset + R]
@@ -200,11 +236,14 @@ class _NTXentHipFn(torch.autograd.Function):
             ops.nt_transpose_cols(zn, znT, col_offset)
             s_loc = ops.nt_fwd_splits(R, R)
             s_rem = ops.nt_fwd_splits(R, Ccols - R)
-            part = torch.empty(((s_loc + 2 * s_rem) * R * 3,), device=dev, dtype=torch.float32)
-            ops.nt_forward_range(znT, R, col_offset, n, inv_t, part, col_offset, col_offset + R,
-                                 s_loc, 0)  # overlaps the exchange
+            part = torch.empty(((s_loc + 2 * s_rem) * R * npart,), device=dev,
+                               dtype=torch.float32)
+            # the rank's own block first, with its own labels (overlaps the exchange)
+            score(y_loc, col_offset, col_offset, col_offset + R, s_loc, 0)
             cur.wait_stream(side)
             zb_all.record_stream(cur)
+            if labelled:
+                ycol.record_stream(cur)
             del pre_keep  # (the head's per-view gather buffers: the side stream is joined)
             # every row in one launch each (this rank's block is rewritten with identical
             # values, after the local scoring read it: same stream)
@@ -214,25 +253,27 @@ class _NTXentHipFn(torch.autograd.Function):
             for lo, hi in ((0, col_offset), (col_offset + R, Ccols)):
                 if hi > lo:
                     sp = max(1, (s_rem * (hi - lo) + (Ccols - R) - 1) // (Ccols - R))
-                    ops.nt_forward_range(znT, R, col_offset, n, inv_t, part, lo, hi, sp, nsp)
+                    score(ycol, 0, lo, hi, sp, nsp)
                     nsp += sp
-            ops.nt_finish(part, R, nsp, lse, rows)
+            finish(nsp)
         else:
             zn = torch.empty((R, D), device=dev, dtype=torch.float32)
             inv = torch.empty((R,), device=dev, dtype=torch.float32)
             ops.nt_normalize(zb, zn, inv)
             zall = zn
+            ycol = y_loc
             col_offset = 0
             Ccols = R
             znT = torch.empty((D, Ccols), device=dev, dtype=torch.float32)
             ops.nt_transpose(zall, znT)
             splits = ops.nt_fwd_splits(R, Ccols)
-            part = torch.empty((splits * R * 3,), device=dev, dtype=torch.float32)
-            ops.nt_forward(znT, R, col_offset, n, inv_t, part, splits, lse, rows)
+            part = torch.empty((splits * R * npart,), device=dev, dtype=torch.float32)
+            score(ycol, 0, 0, Ccols, splits, 0)
+            finish(splits)
         out = torch.empty((1,), device=dev, dtype=torch.float32)
         scale = 1.0 / R if reduction == "mean" else 1.0
         ops.nt_reduce_loss(rows, scale, out)
-        ctx.save_for_backward(zn, zall, znT, lse, inv)
+        ctx.save_for_backward(zn, zall, znT, lse, inv, inv_cnt, ycol)
         ctx.cfg = (n, inv_t, scale, col_offset, gather, st, z.dtype)
         return out.view(())
 
@@ -240,18 +281,26 @@ class _NTXentHipFn(torch.autograd.Function):
     def backward(ctx, gout):
         from ..ops import _ext
         ops = _ext.ops()
-        zn, zall, znT, lse, inv = ctx.saved_tensors
+        zn, zall, znT, lse, inv, inv_cnt, ycol = ctx.saved_tensors
         n, inv_t, scale, col_offset, gather, st, zdtype = ctx.cfg
         R, D = zn.shape
         Ccols = zall.shape[0]
         dev = zn.device
         g = gout.reshape(1).float().contiguous()
+
+        def grad_pass(row_mode, part, splits, out):
+            if ycol is not None:
+                ops.nt_sup_backward_part(row_mode, zall, znT, lse, inv_cnt, ycol, R, col_offset,
+                                         n, inv_t, scale, g, part, splits, out)
+            else:
+                ops.nt_backward_part(row_mode, zall, znT, lse, R, col_offset, n, inv_t, scale, g,
+                                     part, splits, out)
+
         s_col = ops.nt_bwd_splits(Ccols, R)
         part2 = torch.empty((s_col * Ccols * D,), device=dev, dtype=torch.float32)
         d_cols = torch.empty((Ccols, D), device=dev, dtype=torch.float32)
-        ops.nt_backward_part(False, zall, znT, lse, R, col_offset, n, inv_t, scale, g, part2,
-                             s_col, d_cols)
-        overlap = gather and st.comm and dev.type == "cuda"
+        grad_pass(False, part2, s_col, d_cols)
+        overlap = gather and st.comm
         if overlap:
             # global negatives: only this rank's slice of the column gradient is needed, so a
             # reduce-scatter (1/W of an all-reduce's bytes over xGMI) — issued on a side stream
@@ -271,151 +320,7 @@ class _NTXentHipFn(torch.autograd.Function):
         s_row = ops.nt_bwd_splits(R, Ccols)
         part = torch.empty((s_row * R * D,), device=dev, dtype=torch.float32)
         d_rows = torch.empty((R, D), device=dev, dtype=torch.float32)
-        ops.nt_backward_part(True, zall, znT, lse, R, col_offset, n, inv_t, scale, g, part, s_row,
-                             d_rows)
-        if overlap:
-            cur.wait_stream(side)
-            d_rows += mine
-        elif gather and st.comm:
-            mine = torch.empty((R, D), device=dev, dtype=torch.float32)
-            dist.reduce_scatter_tensor(mine, d_cols, group=st.group)
-            d_rows += mine
-        else:
-            d_rows += d_cols[col_offset:col_offset + R]
-        if zdtype == torch.bfloat16:
-            dz = torch.empty((R, D), device=dev, dtype=torch.bfloat16)
-            ops.nt_normalize_backward(zn, inv, d_rows, dz, None)
-        else:
-            dz = torch.empty((R, D), device=dev, dtype=torch.float32)
-            ops.nt_normalize_backward(zn, inv, d_rows, None, dz)
-        return dz, None, None, None, None, None
-
-
-class _SupConHipFn(torch.autograd.Function):
-    """The label-mode kernels (``nt_sup_*``): the structure of :class:`_NTXentHipFn`, with the
-    rank's view-expanded int32 label block built on the device (``nt_expand_labels``) and, for
-    the gathered loss, all-gathered on the side stream right behind z."""
-
-    @staticmethod
-    def forward(ctx, z, y, n, temperature, reduction, gather, st):
-        from ..ops import _ext
-        ops = _ext.ops()
-        R, D = z.shape
-        dev = z.device
-        zb = z.contiguous() if z.dtype == torch.bfloat16 else z.to(torch.bfloat16).contiguous()
-        inv_t = 1.0 / temperature
-        lse = torch.empty((R,), device=dev, dtype=torch.float32)
-        inv_cnt = torch.empty((R,), device=dev, dtype=torch.float32)
-        rows = torch.empty((R,), device=dev, dtype=torch.float32)
-        y_loc = torch.empty((R,), device=dev, dtype=torch.int32)
-        ops.nt_expand_labels(y, None, 2, y_loc)
-        if gather and st.comm:
-            W = st.world_size
-            col_offset = st.rank * R
-            Ccols = W * R
-            cur = torch.cuda.current_stream(dev)
-            side = _side_stream(dev)
-            side.wait_stream(cur)
-            pre = take_pregather(zb)
-            ipc = getattr(st, "ipc", None)
-            ycol = torch.empty((Ccols,), device=dev, dtype=torch.int32)
-            if pre is not None and tuple(pre[0].shape) == (Ccols, D):
-                zb_all, pre_keep = pre
-            else:
-                pre_keep = pre
-                zb_all = torch.empty((Ccols, D), device=dev, dtype=torch.bfloat16)
-                with torch.cuda.stream(side):
-                    if ipc is not None:
-                        ipc.all_gather(("ntxent", "z"), zb, zb_all)
-                    else:
-                        dist.all_gather_into_tensor(zb_all, zb, group=st.group)
-            with torch.cuda.stream(side):  # the labels: one more small collective, same wait
-                if ipc is not None:
-                    ipc.all_gather(("ntxent", "y"), y_loc, ycol)
-                else:
-                    dist.all_gather_into_tensor(ycol, y_loc, group=st.group)
-            zall = torch.empty((Ccols, D), device=dev, dtype=torch.float32)
-            inv_all = torch.empty((Ccols,), device=dev, dtype=torch.float32)
-            zn = zall[col_offset:col_offset + R]
-            inv = inv_all[col_offset:col_offset + R]
-            znT = torch.empty((D, Ccols), device=dev, dtype=torch.float32)
-            ops.nt_normalize(zb, zn, inv)
-            ops.nt_transpose_cols(zn, znT, col_offset)
-            s_loc = ops.nt_fwd_splits(R, R)
-            s_rem = ops.nt_fwd_splits(R, Ccols - R)
-            part = torch.empty(((s_loc + 2 * s_rem) * R * 4,), device=dev, dtype=torch.float32)
-            # the rank's own block first, with its own labels (overlaps the exchange)
-            ops.nt_sup_forward_range(znT, y_loc, col_offset, R, col_offset, n, inv_t, part,
-                                     col_offset, col_offset + R, s_loc, 0)
-            cur.wait_stream(side)
-            zb_all.record_stream(cur)
-            ycol.record_stream(cur)
-            del pre_keep
-            ops.nt_normalize(zb_all, zall, inv_all)
-            ops.nt_transpose(zall, znT)
-            nsp = s_loc
-            for lo, hi in ((0, col_offset), (col_offset + R, Ccols)):
-                if hi > lo:
-                    sp = max(1, (s_rem * (hi - lo) + (Ccols - R) - 1) // (Ccols - R))
-                    ops.nt_sup_forward_range(znT, ycol, 0, R, col_offset, n, inv_t, part, lo, hi,
-                                             sp, nsp)
-                    nsp += sp
-            ops.nt_sup_finish(part, R, nsp, lse, inv_cnt, rows)
-        else:
-            zn = torch.empty((R, D), device=dev, dtype=torch.float32)
-            inv = torch.empty((R,), device=dev, dtype=torch.float32)
-            ops.nt_normalize(zb, zn, inv)
-            zall = zn
-            ycol = y_loc
-            col_offset = 0
-            Ccols = R
-            znT = torch.empty((D, Ccols), device=dev, dtype=torch.float32)
-            ops.nt_transpose(zall, znT)
-            splits = ops.nt_fwd_splits(R, Ccols)
-            part = torch.empty((splits * R * 4,), device=dev, dtype=torch.float32)
-            ops.nt_sup_forward_range(znT, ycol, 0, R, col_offset, n, inv_t, part, 0, Ccols,
-                                     splits, 0)
-            ops.nt_sup_finish(part, R, splits, lse, inv_cnt, rows)
-        out = torch.empty((1,), device=dev, dtype=torch.float32)
-        scale = 1.0 / R if reduction == "mean" else 1.0
-        ops.nt_reduce_loss(rows, scale, out)
-        ctx.save_for_backward(zn, zall, znT, lse, inv, inv_cnt, ycol)
-        ctx.cfg = (n, inv_t, scale, col_offset, gather, st, z.dtype)
-        return out.view(())
-
-    @staticmethod
-    def backward(ctx, gout):
-        from ..ops import _ext
-        ops = _ext.ops()
-        zn, zall, znT, lse, inv, inv_cnt, ycol = ctx.saved_tensors
-        n, inv_t, scale, col_offset, gather, st, zdtype = ctx.cfg
-        R, D = zn.shape
-        Ccols = zall.shape[0]
-        dev = zn.device
-        g = gout.reshape(1).float().contiguous()
-        s_col = ops.nt_bwd_splits(Ccols, R)
-        part2 = torch.empty((s_col * Ccols * D,), device=dev, dtype=torch.float32)
-        d_cols = torch.empty((Ccols, D), device=dev, dtype=torch.float32)
-        ops.nt_sup_backward_part(False, zall, znT, lse, inv_cnt, ycol, R, col_offset, n, inv_t,
-                                 scale, g, part2, s_col, d_cols)
-        overlap = gather and st.comm and dev.type == "cuda"
-        if overlap:
-            # the column gradient's reduce-scatter, as in NT-Xent (under the row pass)
-            cur = torch.cuda.current_stream(dev)
-            side = _side_stream(dev)
-            side.wait_stream(cur)
-            mine = torch.empty((R, D), device=dev, dtype=torch.float32)
-            with torch.cuda.stream(side):
-                ipc = getattr(st, "ipc", None)
-                if ipc is not None:
-                    ipc.reduce_scatter(("ntxent", "dcols"), d_cols, mine)
-                else:
-                    dist.reduce_scatter_tensor(mine, d_cols, group=st.group)
-        s_row = ops.nt_bwd_splits(R, Ccols)
-        part = torch.empty((s_row * R * D,), device=dev, dtype=torch.float32)
-        d_rows = torch.empty((R, D), device=dev, dtype=torch.float32)
-        ops.nt_sup_backward_part(True, zall, znT, lse, inv_cnt, ycol, R, col_offset, n, inv_t,
-                                 scale, g, part, s_row, d_rows)
+        grad_pass(True, part, s_row, d_rows)
         if overlap:
             cur.wait_stream(side)
             d_rows += mine
@@ -460,19 +365,12 @@ class NTXent(nn.Module):
             n = z.shape[0] // 2
         st = pstate.get()
         R, D = z.shape
-        if self.supervised:
-            if labels is None:
-                raise ValueError("the supervised loss (loss.supervised) needs labels")
-            y = _check_labels(labels, n, z.device)
-            if (z.is_cuda and self.reduction != "none" and registry.use_hip(z) and R % 16 == 0
-                    and D in (32, 64, 128, 256)):
-                return _SupConHipFn.apply(z, y, n, self.temperature, self.reduction,
-                                          self.gather, st)
-            return sup_con_torch(z, n, y, self.temperature, self.reduction, self.gather,
-                                 st.group, st.world_size, st.rank)
-        if labels is not None:
+        if self.supervised and labels is None:
+            raise ValueError("the supervised loss (loss.supervised) needs labels")
+        if labels is not None and not self.supervised:
             raise ValueError("labels were given but the loss is not supervised "
                              "(loss.supervised)")
+        y = _check_labels(labels, n, z.device) if self.supervised else None
         if self.gather == "ring" and st.comm and st.world_size > 1:
             # global negatives with the column blocks circulating around the ranks (loss/ring.py)
             from .ring import nt_xent_ring
@@ -481,7 +379,10 @@ class NTXent(nn.Module):
             return nt_xent_ring(z, n, self.temperature, st.group, st.world_size, st.rank)
         if (z.is_cuda and self.reduction != "none" and registry.use_hip(z) and R % 16 == 0
                 and D in (32, 64, 128, 256)):
-            return _NTXentHipFn.apply(z, n, self.temperature, self.reduction, self.gather, st)
+            return _NTXentHipFn.apply(z, y, n, self.temperature, self.reduction, self.gather, st)
+        if self.supervised:
+            return sup_con_torch(z, n, y, self.temperature, self.reduction, self.gather,
+                                 st.group, st.world_size, st.rank)
         return nt_xent_torch(z, n, self.temperature, self.reduction, self.gather, st.group,
                              st.world_size, st.rank)
 

@@ -87,10 +87,14 @@ def test_supcon_fp32_input_gradient():
     assert zh.grad.dtype == torch.float32 and _rel(zh.grad, zr.grad) < 1e-2
 
 
-@pytest.mark.parametrize("n", [24, 256])
-def test_distinct_labels_are_ntxent_bitwise(n):
+@pytest.mark.parametrize("n,D", [
+    pytest.param(24, 128, id="24"), pytest.param(256, 128, id="256"),
+    # every D instantiation at R = 48: three 16-row tiles, no multiple of 32, a single split
+    pytest.param(24, 32, id="24-32"), pytest.param(24, 64, id="24-64"),
+    pytest.param(24, 256, id="24-256")])
+def test_distinct_labels_are_ntxent_bitwise(n, D):
     from simclr_amd.loss.ntxent import NTXent, SupCon
-    D, tau = 128, 0.5
+    tau = 0.5
     z = _z(n, D, n)
     y = torch.randperm(n, device=DEV) * 7 - 50  # distinct, unordered, some negative
     za = z.clone().requires_grad_(True)
@@ -101,6 +105,43 @@ def test_distinct_labels_are_ntxent_bitwise(n):
     lb.backward()
     assert torch.equal(la, lb), (float(la), float(lb))
     assert torch.equal(za.grad, zb.grad)
+
+
+def test_unaligned_labels_take_the_scalar_loads_bitwise():
+    """A label array that is 4- but not 16-byte aligned takes the kernels' non-vectorised label
+    loads (every buffer the loss allocates itself is 16-byte aligned): forward partials, lse,
+    1/|P|, the row losses and both gradient passes equal those of the aligned array."""
+    ops = torch.ops.simclr_amd
+    n, D, inv_t = 24, 64, 2.0
+    R = 2 * n
+    zn = torch.empty(R, D, device=DEV)
+    inv = torch.empty(R, device=DEV)
+    ops.nt_normalize(_z(n, D, 2), zn, inv)
+    znT = torch.empty(D, R, device=DEV)
+    ops.nt_transpose(zn, znT)
+    y = (torch.arange(R, device=DEV) % n % 5).to(torch.int32)
+    buf = torch.zeros(R + 8, device=DEV, dtype=torch.int32)
+    buf[1:1 + R] = y
+    assert y.data_ptr() % 16 == 0 and buf[1:1 + R].data_ptr() % 16 == 4
+    g = torch.full((1,), 0.7, device=DEV)
+    res = []
+    for ycol in (y, buf[1:1 + R]):
+        s_fwd = ops.nt_fwd_splits(R, R)
+        part = torch.empty(s_fwd * R * 4, device=DEV)
+        lse, inv_cnt, rows = (torch.empty(R, device=DEV) for _ in range(3))
+        ops.nt_sup_forward_range(znT, ycol, 0, R, 0, n, inv_t, part, 0, R, s_fwd, 0)
+        ops.nt_sup_finish(part, R, s_fwd, lse, inv_cnt, rows)
+        s_bwd = ops.nt_bwd_splits(R, R)
+        ws = torch.empty(s_bwd * R * D, device=DEV)
+        d_cols, d_rows = torch.empty(R, D, device=DEV), torch.empty(R, D, device=DEV)
+        ops.nt_sup_backward_part(False, zn, znT, lse, inv_cnt, ycol, R, 0, n, inv_t, 1.0 / R, g,
+                                 ws, s_bwd, d_cols)
+        ops.nt_sup_backward_part(True, zn, znT, lse, inv_cnt, ycol, R, 0, n, inv_t, 1.0 / R, g,
+                                 ws, s_bwd, d_rows)
+        res.append((part, lse, inv_cnt, rows, d_cols, d_rows))
+    for a, b in zip(*res):
+        assert torch.equal(a, b)  # (a NaN would not compare equal)
+    assert float(res[0][2].min()) < 1.0 and res[0][5].abs().max() > 0  # (several positives)
 
 
 def test_repeatable():

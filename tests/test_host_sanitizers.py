@@ -25,7 +25,7 @@ SAN = ["-Xarch_host", "-fsanitize=address", "-Xarch_host", "-fsanitize=undefined
 
 def _digest() -> str:
     h = hashlib.sha256()
-    for p in [ROOT / "tools" / "host_check.cpp", CSRC / "kernels.h", CSRC / "common.h",
+    for p in [ROOT / "tools" / "host_check.cpp", CSRC / "kernels.h", CSRC / "common.h", CSRC / "contrast.h",
               *[CSRC / u for u in UNITS]]:
         h.update(p.read_bytes())
     return h.hexdigest()[:16]
