@@ -159,6 +159,25 @@ def check_eval_conf(cfg) -> None:
         k, t = p.get("knn_k"), p.get("knn_t")
         _check(k is None or k >= 1, "parameter.knn_k must be >= 1")
         _check(t is None or t > 0.0, "parameter.knn_t must be > 0")
+    if p.get("classifier") == "kmeans":
+        _check_kmeans(cfg)
+
+
+def _check_kmeans(cfg) -> None:
+    """The ``parameter.kmeans_*`` keys of the k-means probe, within the op's limits
+    (``ops.kmeans.check_limits``); an unset ``kmeans_k`` is the data set's class count."""
+    from ..ops import kmeans
+    p, e = cfg["parameter"], cfg["experiment"]
+    _check(p.get("sweep_lr") is None and p.get("sweep_decay") is None,
+           "parameter.sweep_lr / parameter.sweep_decay need parameter.classifier=linear")
+    K = p.get("kmeans_k")
+    if K is None:
+        K = {"cifar10": 10, "cifar100": 100}.get(e.get("name"))
+    R, T = p.get("kmeans_restarts"), p.get("kmeans_iters")
+    try:
+        kmeans.check_limits(K, 8 if R is None else R, 50 if T is None else T)
+    except ValueError as err:
+        raise AssertionError("parameter." + str(err)) from None
 
 
 def check_save_features_conf(cfg) -> None:

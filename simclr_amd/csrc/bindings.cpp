@@ -1476,6 +1476,100 @@ void knn_vote_op(const Tensor& vals, const Tensor& idx, const Tensor& labels, in
            f32w(scores, "scores"), rank.data_ptr<int>(), cur_stream());
 }
 
+// ------------------------------------------------------------------------------- k-means probe
+// shared geometry checks: xn [N][Fp] bf16, cmat [R * Kp][Fp] bf16, a / s [R][N], counts [R * Kp],
+// changed [R][Tp1], it [1]; every size is checked here, before any launch
+struct KmGeom { int N, Fp, K, Kp, R, Tp1; };
+
+KmGeom km_geometry(const char* op, const Tensor& xn, const Tensor& cmat, int64_t K, int64_t R,
+                   const Tensor& a, const Tensor* s, const Tensor& counts, const Tensor* changed,
+                   const Tensor* it, bool fit) {
+  TORCH_CHECK(xn.dim() == 2 && cmat.dim() == 2, op, ": xn [N][Fp], cmat [R * Kp][Fp]");
+  const int64_t N = xn.size(0), Fp = xn.size(1);
+  TORCH_CHECK(Fp >= km_kstep() && Fp % km_kstep() == 0 && Fp <= km_max_fp(), op,
+              ": Fp must be a multiple of ", km_kstep(), " and <= ", km_max_fp(), ", got ", Fp);
+  TORCH_CHECK(N >= 1 && N * Fp < (1ll << 31), op, ": N must be >= 1 with N * Fp < 2^31, got N ", N,
+              " Fp ", Fp);
+  TORCH_CHECK(R >= 1 && R <= km_max_restarts(), op, ": R must be in [1, ", km_max_restarts(),
+              "], got ", R);
+  TORCH_CHECK(K >= 2 && K <= km_max_cols(), op, ": K must be in [2, ", km_max_cols(), "], got ", K);
+  TORCH_CHECK(!fit || K <= N, op, ": K must be <= N, got K ", K, " N ", N);
+  const int64_t Kp = (K + 15) / 16 * 16;
+  TORCH_CHECK(R * Kp <= km_max_cols(), op, ": R * Kp must be <= ", km_max_cols(), ", got R ", R,
+              " Kp ", Kp);
+  TORCH_CHECK(cmat.size(0) == R * Kp && cmat.size(1) == Fp, op, ": cmat must be [R * Kp][Fp] = [",
+              R * Kp, "][", Fp, "], got [", cmat.size(0), "][", cmat.size(1), "]");
+  check_dev(a, at::kInt, "a");
+  TORCH_CHECK(a.dim() == 2 && a.size(0) == R && a.size(1) == N, op, ": a must be [R][N]");
+  if (s) TORCH_CHECK(s->dim() == 2 && s->size(0) == R && s->size(1) == N, op, ": s must be [R][N]");
+  check_dev(counts, at::kInt, "counts");
+  TORCH_CHECK(counts.numel() == R * Kp, op, ": counts must be [R * Kp]");
+  int64_t Tp1 = 1;
+  if (changed) {
+    check_dev(*changed, at::kInt, "changed");
+    TORCH_CHECK(changed->dim() == 2 && changed->size(0) == R && changed->size(1) >= 1, op,
+                ": changed must be [R][iterations + 1]");
+    Tp1 = changed->size(1);
+  }
+  if (it) {
+    check_dev(*it, at::kInt, "it");
+    TORCH_CHECK(it->numel() == 1, op, ": it must hold one int32");
+  }
+  return {(int)N, (int)Fp, (int)K, (int)Kp, (int)R, (int)Tp1};
+}
+
+void kmeans_assign_op(const Tensor& xn, const Tensor& cmat, int64_t K, int64_t R, const Tensor& a,
+                      const Tensor& s, const Tensor& counts, const Tensor& changed,
+                      const Tensor& it) {
+  const KmGeom g = km_geometry("kmeans_assign", xn, cmat, K, R, a, &s, counts, &changed, &it, false);
+  km_assign(bf(xn, "xn"), bf(cmat, "cmat"), g.N, g.Fp, g.K, g.Kp, g.R, a.data_ptr<int>(),
+            f32w(s, "s"), counts.data_ptr<int>(), changed.data_ptr<int>(), it.data_ptr<int>(), g.Tp1,
+            cur_stream());
+}
+
+void kmeans_update_op(const Tensor& xn, const Tensor& a, int64_t K, int64_t R, const Tensor& counts,
+                      const Tensor& cmat, const c10::optional<Tensor>& S, const Tensor& it) {
+  const KmGeom g = km_geometry("kmeans_update", xn, cmat, K, R, a, nullptr, counts, nullptr, &it,
+                               false);
+  float* Sp = optf32w(S, "S");
+  TORCH_CHECK(!Sp || (S->dim() == 2 && S->size(0) == g.R * g.Kp && S->size(1) == g.Fp),
+              "kmeans_update: S must be [R * Kp][Fp]");
+  at::Tensor slab = at::empty({(int64_t)km_slab_floats(g.N, g.Fp, g.R * g.Kp)},
+                              xn.options().dtype(at::kFloat));
+  km_update(bf(xn, "xn"), a.data_ptr<int>(), g.N, g.Fp, g.K, g.Kp, g.R, counts.data_ptr<int>(),
+            bfw(cmat, "cmat"), Sp, slab.data_ptr<float>(), it.data_ptr<int>(), cur_stream());
+}
+
+// T iterations of assign + update, the final assign and the objectives; nothing is read back and
+// no launch argument depends on the iteration (the device counter `it` selects changed's column)
+void kmeans_fit_op(const Tensor& xn, const Tensor& cmat, int64_t K, int64_t R, int64_t T,
+                   const Tensor& a, const Tensor& s, const Tensor& counts, const Tensor& changed,
+                   const Tensor& J) {
+  TORCH_CHECK(T >= 1 && T <= 1000, "kmeans_fit: T must be in [1, 1000], got ", T);
+  const KmGeom g = km_geometry("kmeans_fit", xn, cmat, K, R, a, &s, counts, &changed, nullptr, true);
+  TORCH_CHECK(g.Tp1 == T + 1, "kmeans_fit: changed must be [R][T + 1]");
+  check_dev(J, at::kDouble, "J");
+  TORCH_CHECK(J.numel() == R, "kmeans_fit: J must be [R]");
+  const uint16_t* X = bf(xn, "xn");
+  uint16_t* C = bfw(cmat, "cmat");
+  float* sp = f32w(s, "s");
+  hipStream_t st = cur_stream();
+  at::Tensor slab = at::empty({(int64_t)km_slab_floats(g.N, g.Fp, g.R * g.Kp)},
+                              xn.options().dtype(at::kFloat));
+  at::Tensor it = at::zeros({1}, xn.options().dtype(at::kInt));
+  hipMemsetAsync(a.data_ptr(), 0xff, sizeof(int) * (size_t)g.R * g.N, st);  // -1: no assignment yet
+  hipMemsetAsync(counts.data_ptr(), 0, sizeof(int) * (size_t)g.R * g.Kp, st);
+  hipMemsetAsync(changed.data_ptr(), 0, sizeof(int) * (size_t)g.R * g.Tp1, st);
+  for (int64_t t = 0; t <= T; ++t) {
+    km_assign(X, C, g.N, g.Fp, g.K, g.Kp, g.R, a.data_ptr<int>(), sp, counts.data_ptr<int>(),
+              changed.data_ptr<int>(), it.data_ptr<int>(), g.Tp1, st);
+    if (t < T)
+      km_update(X, a.data_ptr<int>(), g.N, g.Fp, g.K, g.Kp, g.R, counts.data_ptr<int>(), C, nullptr,
+                slab.data_ptr<float>(), it.data_ptr<int>(), st);
+  }
+  km_objective(sp, g.R, g.N, J.data_ptr<double>(), st);
+}
+
 // ------------------------------------------------------------------------------- probe sweep
 // shared geometry checks: X [N][Fp] bf16, idx [rows] int64, G configurations of C classes
 int64_t probe_geometry(const char* op, const Tensor& X, const Tensor& idx, const Tensor& Wsh,
@@ -1726,6 +1820,9 @@ TORCH_LIBRARY(simclr_amd, m) {
   m.def("knn_scratch_bytes(int Q, int N, int k) -> int", &knn_scratch_bytes_op);
   m.def("knn_kstep() -> int", []() -> int64_t { return knn_kstep(); });
   m.def("knn_vote(Tensor vals, Tensor idx, Tensor labels, int C, float temperature, Tensor targets, Tensor(a!) scores, Tensor(b!) rank) -> ()", &knn_vote_op);
+  m.def("kmeans_assign(Tensor xn, Tensor cmat, int K, int R, Tensor(a!) a, Tensor(b!) s, Tensor(c!) counts, Tensor(d!) changed, Tensor it) -> ()", &kmeans_assign_op);
+  m.def("kmeans_update(Tensor xn, Tensor a, int K, int R, Tensor(a!) counts, Tensor(b!) cmat, Tensor(c!)? S, Tensor(d!) it) -> ()", &kmeans_update_op);
+  m.def("kmeans_fit(Tensor xn, Tensor(a!) cmat, int K, int R, int T, Tensor(b!) a, Tensor(c!) s, Tensor(d!) counts, Tensor(e!) changed, Tensor(f!) J) -> ()", &kmeans_fit_op);
   m.def("maxpool_fwd(Tensor x, Tensor(a!) y, Tensor(b!) arg, int K, int S, int P) -> ()", &maxpool_fwd_op);
   m.def("maxpool_bwd(Tensor dy, Tensor arg, Tensor(a!) dx, int K, int S, int P) -> ()", &maxpool_bwd_op);
   m.def("stem_s2d(Tensor img, int creal, int P, Tensor(a!) xs) -> ()", &stem_s2d_op);

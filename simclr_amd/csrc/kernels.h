@@ -353,6 +353,24 @@ void knn_topk(const uint16_t* Qn, const uint16_t* Bn, int Q, int N, int Dp, int 
 void knn_vote(const float* vals, const int* idx, const int64_t* labels, const int64_t* targets,
               int Q, int k, int N, int C, float inv_t, float* scores, int* rank, hipStream_t s);
 
+// ---- kmeans.hip: spherical k-means probe (R restarts in the same launches: fused similarity /
+// top-1 assignment, one-hot GEMM centroid update, slab merge + normalise)
+int km_kstep();         // Fp is F rounded up to this
+int km_max_restarts();  // R
+int km_max_cols();      // R * Kp
+int km_max_fp();
+int km_splits(int N, int Fp);                    // row splits of the update: independent of R
+size_t km_slab_floats(int N, int Fp, int RK);    // fp32 scratch of the update
+// X [N][Fp], C [R * Kp][Fp] bf16; a [R][N] (read as the previous assignment, then overwritten),
+// s [R][N]; counts [R * Kp] += rows per cluster; changed [R][Tp1], column *it += changed rows
+void km_assign(const uint16_t* X, const uint16_t* C, int N, int Fp, int K, int Kp, int R, int* a,
+               float* s, int* counts, int* changed, const int* it, int Tp1, hipStream_t st);
+// C <- normalised sums of the rows assigned by a (S [R * Kp][Fp], optional: the merged sums);
+// clears counts, *it += 1
+void km_update(const uint16_t* X, const int* a, int N, int Fp, int K, int Kp, int R, int* counts,
+               uint16_t* C, float* S, float* slab, int* it, hipStream_t st);
+void km_objective(const float* s, int R, int N, double* J, hipStream_t st);
+
 // ---- probe.hip: linear-probe sweep (G classifiers on one feature batch: fused forward / CE /
 // gradient, fused weight gradient / Nesterov SGD update)
 int probe_kstep();        // Fp is F rounded up to this

@@ -32,7 +32,7 @@ import torch.nn.functional as F
 
 from ..models.heads import CentroidClassifier, LinearClassifier, NonLinearClassifier
 from ..ops.classify import ce_rank, cross_entropy
-from ..ops import probe_sweep
+from ..ops import kmeans, probe_sweep
 from ..ops.knn import knn_topk, knn_vote
 from ..utils.misc import cfg_get
 from ..optim.schedule import cosine_lr
@@ -94,6 +94,42 @@ def knn_eval(bank: DownstreamDataset, query: DownstreamDataset, num_classes: int
     if return_scores:
         return c[0] / n, c[1] / n, scores
     return c[0] / n, c[1] / n
+
+
+@torch.no_grad()
+def kmeans_eval(cfg, train: DownstreamDataset, val: DownstreamDataset, num_classes: int) -> Dict:
+    """Spherical k-means on the train features (``ops/kmeans.py`` holds the contract): R restarts
+    in one pass, the best by objective scored against the labels on train and val (NMI, ARI, purity
+    and the matched accuracy; val with the train matching)."""
+    K = cfg_get(cfg, "parameter.kmeans_k", None)
+    K = int(num_classes if K is None else K)
+    R = int(cfg_get(cfg, "parameter.kmeans_restarts", 8))
+    T = int(cfg_get(cfg, "parameter.kmeans_iters", 50))
+    if sweep_values(cfg) is not None:
+        raise ValueError("parameter.sweep_lr / parameter.sweep_decay need parameter.classifier=linear")
+    fit = kmeans.kmeans_fit(train.data, K, R, T, seed=int(cfg_get(cfg, "parameter.seed", 0)))
+    b = fit.best
+    tr_table = kmeans.contingency(fit.a[b], train.targets, K, num_classes)
+    va_a, _ = kmeans.kmeans_assign(val.data.to(train.data.device), fit.centroids[b])
+    va_table = kmeans.contingency(va_a, val.targets, K, num_classes)
+    match = kmeans.cluster_matching(tr_table)
+    tr, va = kmeans.cluster_scores(tr_table, match), kmeans.cluster_scores(va_table, match)
+    logging.info("train acc: {}, val acc: {}".format(tr["acc"], va["acc"]))
+    n = max(1, len(train))
+    out = {}
+    for m in ("acc", "nmi", "ari", "purity"):
+        out["train_" + m] = tr[m]
+        out["val_" + m] = va[m]
+    out.update({
+        "kmeans_k": K,
+        "kmeans_restarts": R,
+        "kmeans_iters": T,
+        "best": b,
+        "objective": [float(j) / n for j in fit.objective.tolist()],
+        "iterations": kmeans.iterations(fit.changed),
+        "cluster_sizes": [int(c) for c in fit.counts[b].tolist()],
+    })
+    return out
 
 
 def _eval_counts(classifier, ds: DownstreamDataset, top_k: int, batch_size: int,
@@ -276,13 +312,16 @@ def run_probe(cfg, kind: str, train: DownstreamDataset, val: DownstreamDataset, 
             "knn_k": k,
             "knn_t": t,
         }
+    if kind == "kmeans":
+        return kmeans_eval(cfg, train, val, num_classes)
     F_ = train.data.shape[1]
     if kind == "linear":
         clf = LinearClassifier(F_, num_classes).to(device)
     elif kind.replace("-", "") == "nonlinear":
         clf = NonLinearClassifier(F_, num_classes).to(device)
     else:
-        raise ValueError(f"unknown classifier {kind!r} (centroid | knn | linear | nonlinear)")
+        raise ValueError(f"unknown classifier {kind!r} "
+                         "(centroid | knn | kmeans | linear | nonlinear)")
     sv = sweep_values(cfg)
     if sv is not None:
         if kind != "linear":
