@@ -1570,26 +1570,44 @@ void kmeans_fit_op(const Tensor& xn, const Tensor& cmat, int64_t K, int64_t R, i
   km_objective(sp, g.R, g.N, J.data_ptr<double>(), st);
 }
 
-// ------------------------------------------------------------------------------- probe sweep
-// shared geometry checks: X [N][Fp] bf16, idx [rows] int64, G configurations of C classes
-int64_t probe_geometry(const char* op, const Tensor& X, const Tensor& idx, const Tensor& Wsh,
-                       int64_t G, int64_t C) {
-  TORCH_CHECK(X.dim() == 2 && Wsh.dim() == 2, op, ": X [N][Fp], Wsh [G * Cp][Fp]");
-  const int64_t N = X.size(0), Fp = X.size(1), rows = idx.numel();
-  TORCH_CHECK(N >= 1 && N < (1ll << 31), op, ": N must be in [1, 2^31)");
+// ------------------------------------------------------------------------------- linear probes
+// What the sweep and the online probe check alike: features [.][Fp] (bf16, contiguous: bf() checks
+// where the pointer is taken) with Fp a multiple of the kernels' K step; returns Cp = 16 ceil(C / 16)
+int64_t linear_probe_geometry(const char* op, const Tensor& X, int64_t C) {
+  TORCH_CHECK(X.dim() == 2, op, ": features must be [rows][Fp]");
+  const int64_t Fp = X.size(1);
   TORCH_CHECK(Fp >= probe_kstep() && Fp % probe_kstep() == 0 && Fp <= 4096, op,
               ": padded feature width must be a multiple of ", probe_kstep(), " and <= 4096, got ",
               Fp);
+  TORCH_CHECK(C >= 1, op, ": C must be >= 1");
+  return (C + 15) / 16 * 16;
+}
+
+// the forward's gradient outputs, NT columns in all: dlT [NT][ld >= Rp, a multiple of 32] (returns
+// ld), dbp [>= RT][NT] (one row per 16-row tile)
+int64_t linear_probe_grad_bufs(const char* op, const Tensor& dlT, const Tensor& dbp, int64_t NT,
+                               int64_t Rp, int64_t RT) {
+  TORCH_CHECK(dlT.dim() == 2 && dlT.size(0) == NT && dlT.size(1) >= Rp && dlT.size(1) % 32 == 0, op,
+              ": dlT [", NT, "][>= rows rounded up to 32, a multiple of 32]");
+  TORCH_CHECK(dbp.numel() >= RT * NT, op, ": dbp [", RT, "][", NT, "]");
+  return dlT.size(1);
+}
+
+// ------------------------------------------------------------------------------- probe sweep
+// the sweep's own: X [N][Fp], idx [rows] int64, G configurations of C classes
+int64_t probe_geometry(const char* op, const Tensor& X, const Tensor& idx, const Tensor& Wsh,
+                       int64_t G, int64_t C) {
+  const int64_t Cp = linear_probe_geometry(op, X, C);
+  const int64_t N = X.size(0), Fp = X.size(1), rows = idx.numel();
+  TORCH_CHECK(N >= 1 && N < (1ll << 31), op, ": N must be in [1, 2^31)");
   TORCH_CHECK(G >= 1 && G <= probe_max_configs(), op, ": G must be in [1, ", probe_max_configs(),
               "], got ", G);
-  TORCH_CHECK(C >= 1, op, ": C must be >= 1");
-  const int64_t Cp = (C + 15) / 16 * 16;
   TORCH_CHECK(G * Cp <= probe_max_cols(), op, ": G * Cp must be <= ", probe_max_cols(), ", got ",
               G * Cp);
   TORCH_CHECK(rows >= 1 && rows <= probe_max_rows(), op, ": rows must be in [1, ",
               probe_max_rows(), "], got ", rows);
-  TORCH_CHECK(Wsh.size(0) == G * Cp && Wsh.size(1) == Fp, op, ": Wsh must be [", G * Cp, "][", Fp,
-              "]");
+  TORCH_CHECK(Wsh.dim() == 2 && Wsh.size(0) == G * Cp && Wsh.size(1) == Fp, op, ": Wsh must be [",
+              G * Cp, "][", Fp, "]");
   check_dev(idx, at::kLong, "idx");
   return Cp;
 }
@@ -1630,13 +1648,9 @@ void probe_forward_op(const Tensor& X, const Tensor& y, const Tensor& idx, const
     a.rank = rank->data_ptr<int>();
   }
   if (train) {
-    TORCH_CHECK(dlT->dim() == 2 && dlT->size(0) == NT && dlT->size(1) >= Rp &&
-                    dlT->size(1) % 32 == 0,
-                "probe_forward: dlT [G * Cp][>= rows rounded up to 32, a multiple of 32]");
-    TORCH_CHECK(dbp.has_value() && dbp->defined() && dbp->numel() >= (rows + 15) / 16 * NT,
-                "probe_forward: dbp [ceil(rows / 16)][G * Cp]");
+    TORCH_CHECK(dbp.has_value() && dbp->defined(), "probe_forward: dbp goes with dlT");
+    a.ldr = (int)linear_probe_grad_bufs("probe_forward", *dlT, *dbp, NT, Rp, (rows + 15) / 16);
     a.dlT = bfw(*dlT, "dlT");
-    a.ldr = (int)dlT->size(1);
     a.dbp = f32w(*dbp, "dbp");
   }
   probe_forward(a, cur_stream());
@@ -1649,9 +1663,7 @@ void probe_update_op(const Tensor& X, const Tensor& idx, const Tensor& dlT, cons
   const int64_t Cp = probe_geometry("probe_update", X, idx, Wsh, G, C);
   const int64_t rows = idx.numel(), NT = G * Cp, Fp = X.size(1);
   const int64_t Rp = (rows + 31) / 32 * 32;
-  TORCH_CHECK(dlT.dim() == 2 && dlT.size(0) == NT && dlT.size(1) >= Rp && dlT.size(1) % 32 == 0,
-              "probe_update: dlT [G * Cp][>= rows rounded up to 32, a multiple of 32]");
-  TORCH_CHECK(dbp.numel() >= (rows + 15) / 16 * NT, "probe_update: dbp");
+  const int64_t ldr = linear_probe_grad_bufs("probe_update", dlT, dbp, NT, Rp, (rows + 15) / 16);
   TORCH_CHECK(W.numel() == NT * Fp && Mw.numel() == NT * Fp, "probe_update: W, Mw [G * Cp][Fp]");
   TORCH_CHECK(b.numel() == NT && Mb.numel() == NT, "probe_update: b, Mb [G * Cp]");
   TORCH_CHECK(lr0.numel() == G && wd.numel() == G, "probe_update: lr0, wd [G]");
@@ -1668,7 +1680,7 @@ void probe_update_op(const Tensor& X, const Tensor& idx, const Tensor& dlT, cons
   a.C = (int)C;
   a.Cp = (int)Cp;
   a.dlT = bf(dlT, "dlT");
-  a.ldr = (int)dlT.size(1);
+  a.ldr = (int)ldr;
   a.dbp = f32(dbp, "dbp");
   a.W = f32w(W, "W");
   a.Mw = f32w(Mw, "Mw");
@@ -1684,23 +1696,25 @@ void probe_update_op(const Tensor& X, const Tensor& idx, const Tensor& dlT, cons
 }
 
 // ------------------------------------------------------------------------------- online probe
-// shared geometry checks: h [rows][Fp] bf16 (rows = 2n, a multiple of 16), C classes
+// the online probe's own: h [rows][Fp] with rows = 2n a multiple of 16, one configuration, and
+// dlT exactly [Cp][Rp]
 struct OnlineProbeGeom {
   int64_t rows, Rp, Fp, Cp;
 };
 OnlineProbeGeom online_probe_geometry(const char* op, const Tensor& h, int64_t C) {
-  TORCH_CHECK(h.dim() == 2, op, ": h must be [rows][Fp]");
-  OnlineProbeGeom g{h.size(0), (h.size(0) + 31) / 32 * 32, h.size(1), (C + 15) / 16 * 16};
+  const int64_t Cp = linear_probe_geometry(op, h, C);
+  OnlineProbeGeom g{h.size(0), (h.size(0) + 31) / 32 * 32, h.size(1), Cp};
   TORCH_CHECK(g.rows >= 16 && g.rows % 16 == 0 && g.rows <= online_probe_max_rows(), op,
               ": rows must be a multiple of 16 in [16, ", online_probe_max_rows(), "], got ",
               g.rows);
-  TORCH_CHECK(g.Fp >= online_probe_kstep() && g.Fp % online_probe_kstep() == 0 &&
-                  g.Fp <= online_probe_max_fp(),
-              op, ": padded feature width must be a multiple of ", online_probe_kstep(),
-              " and <= ", online_probe_max_fp(), ", got ", g.Fp);
-  TORCH_CHECK(C >= 1 && g.Cp <= online_probe_max_cols(), op, ": C must be in [1, ",
-              online_probe_max_cols(), "], got ", C);
+  TORCH_CHECK(g.Cp <= online_probe_max_cols(), op, ": C must be in [1, ", online_probe_max_cols(),
+              "], got ", C);
   return g;
+}
+void online_probe_grad_bufs(const char* op, const OnlineProbeGeom& g, const Tensor& dlT,
+                            const Tensor& dbp) {
+  const int64_t ld = linear_probe_grad_bufs(op, dlT, dbp, g.Cp, g.Rp, g.rows / 16);
+  TORCH_CHECK(ld == g.Rp, op, ": dlT [Cp][rows rounded up to 32]");
 }
 
 void online_probe_forward_op(const Tensor& h, const Tensor& y, const Tensor& Wsh,
@@ -1716,8 +1730,7 @@ void online_probe_forward_op(const Tensor& h, const Tensor& y, const Tensor& Wsh
   TORCH_CHECK(bias.numel() == g.Cp, op, ": bias [Cp]");
   TORCH_CHECK(Z.numel() >= g.rows * g.Cp, op, ": logits scratch [rows][Cp]");
   TORCH_CHECK(loss.numel() == g.rows && rank.numel() == g.rows, op, ": loss, rank [rows]");
-  TORCH_CHECK(dlT.numel() == g.Cp * g.Rp, op, ": dlT [Cp][rows rounded up to 32]");
-  TORCH_CHECK(dbp.numel() >= g.rows / 16 * g.Cp, op, ": dbp [rows / 16][Cp]");
+  online_probe_grad_bufs(op, g, dlT, dbp);
   check_dev(rank, at::kInt, "rank");
   OnlineProbeFwdArgs a{};
   a.X = bf(h, "h");
@@ -1758,8 +1771,7 @@ void online_probe_wgrad_op(const Tensor& h, const Tensor& dlT, const Tensor& dbp
                            const Tensor& grad, int64_t C) {
   const char* op = "online_probe_wgrad";
   const OnlineProbeGeom g = online_probe_geometry(op, h, C);
-  TORCH_CHECK(dlT.numel() == g.Cp * g.Rp, op, ": dlT [Cp][rows rounded up to 32]");
-  TORCH_CHECK(dbp.numel() >= g.rows / 16 * g.Cp, op, ": dbp [rows / 16][Cp]");
+  online_probe_grad_bufs(op, g, dlT, dbp);
   TORCH_CHECK(grad.numel() == g.Cp * g.Fp + g.Cp, op, ": grad [Cp * Fp + Cp]");
   OnlineProbeGradArgs a{};
   a.X = bf(h, "h");

@@ -40,6 +40,29 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// Transposed staging of a [32 rows][64 columns] bf16 tile into LDS as Xs[column][row] (row stride
+// XT_LD), the K-contiguous B operand of an MFMA whose K runs over the rows.  Thread tid of 256 owns
+// the 16-byte chunk tid & 7 of tile row tid >> 3: xt_load reads it for the tile that starts at row
+// k0 (row(k): the tile's first column in row k; zeros for the rows from kend on, for which row is
+// not called), xt_store scatters its eight values.
+constexpr int XT_ROWS = 32, XT_LD = XT_ROWS + 8;
+
+template <class RowPtr>
+__device__ __forceinline__ u32x4 xt_load(int k0, int kend, int tid, RowPtr row) {
+  const int k = k0 + (tid >> 3);
+  if (k >= kend) return (u32x4){0u, 0u, 0u, 0u};
+  return *(const u32x4*)(row(k) + (tid & 7) * 8);
+}
+
+__device__ __forceinline__ void xt_store(uint16_t* Xs, int tid, u32x4 rx) {
+  const int sk = tid >> 3, sc = tid & 7;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    Xs[(sc * 8 + 2 * i) * XT_LD + sk] = (uint16_t)(rx[i] & 0xffffu);
+    Xs[(sc * 8 + 2 * i + 1) * XT_LD + sk] = (uint16_t)(rx[i] >> 16);
+  }
+}
+
 // Bijective XCD-aware remap of a linear workgroup id (cdna_hip_programming.md §5 / T1):
 // consecutive *logical* ids land on the same XCD (blocks b and b+8 share an XCD).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {

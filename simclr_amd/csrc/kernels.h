@@ -412,8 +412,9 @@ struct ProbeUpdArgs {
 };
 void probe_update(const ProbeUpdArgs& a, hipStream_t s);
 
-// ---- online_probe.hip: one linear classifier trained on the encoder output inside the captured
-// pre-training step; whatever changes per step is read from device memory
+// ---- probe.hip, online probe: one linear classifier trained on the encoder output inside the
+// captured pre-training step, on the sweep's forward and weight-gradient kernels under its own
+// row policy; whatever changes per step is read from device memory
 int online_probe_kstep();     // Fp is F rounded up to this
 int online_probe_max_cols();  // Cp
 int online_probe_max_fp();

@@ -18,7 +18,8 @@
 //   k_km_update     slab[split] = onehot(a)ᵀ · X over the split's rows: block = 128 centroid rows
 //                   x 64 features, K-steps of 32 data rows in ascending order; the one-hot A
 //                   operand is built in registers from the assignments (1.0 / 0.0 are exact in
-//                   bf16), the X tile is transposed through LDS as in k_probe_wgrad_update.
+//                   bf16), the X tile is transposed through LDS by xt_load / xt_store (common.h),
+//                   as in the linear probes' k_linear_wgrad.
 //   k_km_finish     block = one centroid row: merges the slabs in split order, norm in fp64,
 //                   c = bf16(S / max(|S|, 1e-12)); a cluster without rows keeps its centroid bits.
 //                   Clears the row's count for the next assign and advances the device-side
@@ -36,7 +37,7 @@ namespace {
 constexpr int KM_BM = 128, KM_BN = 128, KM_BK = 64, KM_KP = KM_BK + 8;
 constexpr int KM_MAX_R = 16, KM_MAX_COLS = 1024;
 constexpr int KM_NONE = 0x7fffffff;  // index of "no valid similarity seen"
-constexpr int KM_UF = 64, KM_UM = 128, KM_UK = 32, KM_UKP = KM_UK + 8;
+constexpr int KM_UF = 64, KM_UM = 128, KM_UK = XT_ROWS, KM_UKP = XT_LD;
 constexpr int KM_MAX_FP = 4096;
 
 // (v, k) beats (bv, bk) under (sim descending, k ascending)
@@ -196,15 +197,12 @@ __global__ __launch_bounds__(256) void k_km_update(const uint16_t* __restrict__ 
   const int ncnt = min(KM_UM / 16, (RK - n0) / 16);
   const int kbeg = min(N, (int)blockIdx.z * rps), kend = min(N, kbeg + rps);
 
-  // staging: 32 data rows x 8 16-byte chunks of the feature tile, one chunk per thread; the
-  // assignments of the tile's (up to) 8 sixteen-centroid blocks, one value per thread
-  const int sk = tid >> 3, sc = tid & 7;
+  // staging: 32 data rows x 8 16-byte chunks of the feature tile, one chunk per thread (xt_load);
+  // the assignments of the tile's (up to) 8 sixteen-centroid blocks, one value per thread
   const int aq = tid >> 5, ak = tid & 31;
   const int ar = aq < ncnt ? (n0 + 16 * aq) / Kp : 0;
   auto loadx = [&](int k0) -> u32x4 {
-    const int k = k0 + sk;
-    if (k >= kend) return (u32x4){0u, 0u, 0u, 0u};
-    return *(const u32x4*)(X + (size_t)k * Fp + f0 + sc * 8);
+    return xt_load(k0, kend, tid, [&](int k) { return X + (size_t)k * Fp + f0; });
   };
   auto loada = [&](int k0) -> int {
     const int k = k0 + ak;
@@ -223,11 +221,7 @@ __global__ __launch_bounds__(256) void k_km_update(const uint16_t* __restrict__ 
   u32x4 rx = loadx(kbeg);
   int ra = loada(kbeg);
   for (int k0 = kbeg; k0 < kend; k0 += KM_UK) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      Xs[(sc * 8 + 2 * i) * KM_UKP + sk] = (uint16_t)(rx[i] & 0xffffu);
-      Xs[(sc * 8 + 2 * i + 1) * KM_UKP + sk] = (uint16_t)(rx[i] >> 16);
-    }
+    xt_store(Xs, tid, rx);
     As[tid] = ra;
     __syncthreads();
     if (k0 + KM_UK < kend) {

@@ -1,7 +1,7 @@
 """Online linear probe: one linear classifier trained on the stop-gradient encoder output of every
-pre-training step ("linear eval while pre-training"), on the HIP kernels of csrc/online_probe.hip
-on the GPU and as torch ops of the same contract (the twin) elsewhere.  The twin is the CPU / fp32
-path and the tests' oracle.
+pre-training step ("linear eval while pre-training"), on the HIP kernels of csrc/probe.hip (the
+sweep's forward and weight gradient under the online row policy) on the GPU and as torch ops of the
+same contract (the twin) elsewhere.  The twin is the CPU / fp32 path and the tests' oracle.
 
 Contract (both paths):
 
@@ -38,21 +38,12 @@ import torch.distributed as dist
 
 from ..optim.schedule import MODE_WARMUP_COSINE, lr_at
 from . import registry
-from .probe_sweep import _rank
+from .probe_sweep import K_STEP, _ce_twin, padded_classes, padded_features  # noqa: F401
 
-K_STEP = 64       # feature columns are zero-padded to a multiple of it
 MAX_CLASSES = 1024
 MAX_FP = 4096
 MAX_ROWS = 8192   # rows of one kernel call (2n)
 ROW_TILE = 16     # the HIP path needs 2n % ROW_TILE == 0
-
-
-def padded_classes(num_classes: int) -> int:
-    return (num_classes + 15) // 16 * 16
-
-
-def padded_features(num_features: int) -> int:
-    return (num_features + K_STEP - 1) // K_STEP * K_STEP
 
 
 def initial_lr(lr: float, batch: int, linear_schedule: bool) -> float:
@@ -212,18 +203,7 @@ class OnlineProbe:
         xa = x.to(acc)
         t = y.to(device=self.device, dtype=torch.long).repeat(rows // y.numel())
         z = (xa @ self.Wsh[:C, :F].to(acc).t()).float() + self.b[:C]
-        ok = (t >= 0) & (t < C)
-        tc = t.clamp(0, C - 1)
-        onehot = torch.zeros(rows, C, device=self.device, dtype=torch.float32)
-        onehot[torch.arange(rows, device=self.device)[ok], tc[ok]] = 1.0
-        m = z.max(1).values
-        e = torch.exp(z - m[:, None])
-        s = e.sum(1)
-        nan = torch.full((rows,), float("nan"), device=self.device)
-        zt = torch.where(ok, z.gather(1, tc.view(-1, 1)).view(-1), nan)
-        loss = torch.log(s) + m - zt
-        rank = _rank(z, t)
-        d = (e / s[:, None] - onehot) / float(rows)
+        loss, rank, d = _ce_twin(z, t)
         dl = d.to(torch.bfloat16).float() if self.round_operands else d
         self.acc_loss += loss.double().sum()
         self.acc_cnt += torch.stack([(rank == 0).sum(), (rank < self.top_k).sum(),

@@ -114,6 +114,27 @@ def _rank(z: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
     return torch.where(never, torch.full_like(tc.view(-1), C), above.sum(1)).to(torch.int32)
 
 
+def _ce_twin(z: torch.Tensor, t: torch.Tensor, grad: bool = True):
+    """The twins' softmax / CE block on fp32 logits ``z`` [rows][C] and targets ``t`` [rows]:
+    per-row loss (NaN for a target outside [0, C)), the target's rank and, with ``grad``,
+    ``(softmax - onehot) / rows`` (a row without a valid target has no one-hot entry)."""
+    rows, C = z.shape
+    ok = (t >= 0) & (t < C)
+    tc = t.clamp(0, C - 1)
+    m = z.max(1).values
+    e = torch.exp(z - m[:, None])
+    s = e.sum(1)
+    nan = torch.full((rows,), float("nan"), device=z.device)
+    zt = torch.where(ok, z.gather(1, tc.view(-1, 1)).view(-1), nan)
+    loss = torch.log(s) + m - zt
+    rank = _rank(z, t)
+    if not grad:
+        return loss, rank, None
+    onehot = torch.zeros(rows, C, device=z.device, dtype=torch.float32)
+    onehot[torch.arange(rows, device=z.device)[ok], tc[ok]] = 1.0
+    return loss, rank, (e / s[:, None] - onehot) / float(rows)
+
+
 class LinearSweep:
     """State of a sweep: fp32 master weights and momentum, the bf16 shadow and the step counter.
 
@@ -238,22 +259,11 @@ class LinearSweep:
         logits = torch.empty(rows, G, C, device=self.device, dtype=torch.float32)
         dl = torch.zeros(G, rows, C, device=self.device, dtype=torch.float32) if train else None
         db = torch.zeros(G, C, device=self.device, dtype=torch.float32) if train else None
-        onehot = torch.zeros(rows, C, device=self.device, dtype=torch.float32)
-        ok = (t >= 0) & (t < C)
-        tc = t.clamp(0, C - 1)
-        onehot[torch.arange(rows, device=self.device)[ok], tc[ok]] = 1.0
-        nan = torch.full((rows,), float("nan"), device=self.device)
         for g in range(G):  # one configuration at a time, identical shapes: bitwise independent
             z = (xa @ Wv[g, :C].to(acc).t()).float() + bv[g, :C]
-            m = z.max(1).values
-            e = torch.exp(z - m[:, None])
-            s = e.sum(1)
-            zt = torch.where(ok, z.gather(1, tc.view(-1, 1)).view(-1), nan)
-            loss[g] = torch.log(s) + m - zt
-            rank[g] = _rank(z, t)
+            loss[g], rank[g], d = _ce_twin(z, t, train)
             logits[:, g] = z
             if train:
-                d = (e / s[:, None] - onehot) / float(rows)
                 db[g] = d.to(acc).sum(0).float()
                 dl[g] = d.to(torch.bfloat16).float() if self.round_operands else d
         if loss_out is not None:

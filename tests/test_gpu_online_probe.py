@@ -1,5 +1,6 @@
-"""HIP kernels of csrc/online_probe.hip against the torch twin of ``ops/online_probe.py`` (fp64
-accumulation on the same bf16 operands), the captured pre-training step with the probe in it, and
+"""The online probe's HIP kernels (csrc/probe.hip) against the torch twin of
+``ops/online_probe.py`` (fp64 accumulation on the same bf16 operands) and bitwise against the
+sweep's ops, which run the same kernels; the captured pre-training step with the probe in it, and
 the CLI.
 
 Bounds, with u = 2^-24 (fp32 unit roundoff), as tests/test_gpu_probe_sweep.py derives them:
@@ -204,6 +205,79 @@ def test_shapes_outside_the_limits_take_the_twin_and_ops_check_by_name():
     with pytest.raises(RuntimeError, match="online_probe_update: master"):
         ops.online_probe_update(pr.master[:-1], pr.grad, pr.mom, pr.Wsh, pr.lr_t, 0.0, 0.9, 1.0,
                                 10, 64, 64)
+
+
+# ------------------------------------------------------------------ one kernel family
+# (rows, F, C): Cp 16 (one column tile at a time) with a pure-padding row tile (Rp 32); Cp 112
+# (seven column tiles: the last group of four is clamped); Cp 32 with a mostly-padding column tile
+FAMILY_SHAPES = [(16, 64, 10), (48, 96, 100), (32, 64, 17)]
+
+
+def _family_operands(rows, Fd, C):
+    op = _op()
+    W, b, ((h, y32),) = _problem(rows, Fd, C, 3)
+    Cp, Fp, Rp = op.padded_classes(C), op.padded_features(Fd), (rows + 31) // 32 * 32
+    X = torch.zeros(rows, Fp, dtype=torch.bfloat16)
+    X[:, :Fd] = h
+    Wsh = torch.zeros(Cp, Fp, dtype=torch.bfloat16)
+    Wsh[:C, :Fd] = W.to(torch.bfloat16)
+    bias = torch.zeros(Cp)
+    bias[:C] = b
+    return X.to(DEV), y32.to(DEV), Wsh.to(DEV), bias.to(DEV), Cp, Fp, Rp
+
+
+@pytest.mark.parametrize("rows, Fd, C", FAMILY_SHAPES)
+def test_forward_is_bitwise_the_sweeps_forward(rows, Fd, C):
+    """The online probe's forward and the sweep's (G = 1, idx = arange, the labels repeated per
+    view) are one kernel under two row policies: every output has the same bits."""
+    X, y32, Wsh, bias, Cp, Fp, Rp = _family_operands(rows, Fd, C)
+    ops = torch.ops.simclr_amd
+    f32, i32, bf = (dict(device=DEV, dtype=t) for t in (torch.float32, torch.int32, torch.bfloat16))
+    # every output starts from a value that neither kernel writes
+    Zo, Zs = torch.full((rows, Cp), 7.0, **f32), torch.full((rows, Cp), 7.0, **f32)
+    lo, ls = torch.full((rows,), 7.0, **f32), torch.full((rows,), 7.0, **f32)
+    ro, rs = torch.full((rows,), -7, **i32), torch.full((1, rows), -7, **i32)
+    do, ds = torch.full((Cp, Rp), 7.0, **bf), torch.full((Cp, Rp + 32), 7.0, **bf)
+    po, ps = torch.full((rows // 16, Cp), 7.0, **f32), torch.full((rows // 16, Cp), 7.0, **f32)
+    ops.online_probe_forward(X, y32, Wsh, bias, C, Zo, lo, ro, do, po)
+    y = y32.long().repeat(rows // y32.numel())
+    ops.probe_forward(X, y, torch.arange(rows, device=DEV), Wsh, bias, 1, C, Zs, ls, rows, rs, ds,
+                      ps)
+    torch.cuda.synchronize()
+    assert torch.equal(Zo[:rows, :C], Zs[:rows, :C])
+    assert torch.equal(lo, ls) and torch.equal(ro, rs[0])
+    assert torch.equal(do.view(torch.int16), ds[:, :Rp].view(torch.int16))
+    assert not do[C:].any() and not do[:, rows:].any()  # the padding columns and rows: zeros
+    assert bool((ds[:, Rp:] == 7.0).all())              # (the sweep's wider dlT: untouched)
+    assert torch.equal(po, ps)
+    assert bool(torch.isfinite(lo).all()) and int(ro.min()) >= 0 and int(ro.max()) < C
+    assert float(do.float().abs().max()) > 0
+
+
+@pytest.mark.parametrize("rows, Fd, C", FAMILY_SHAPES)
+def test_weight_gradient_is_bitwise_the_sweeps(rows, Fd, C):
+    """The same dlogits and bias partials through ``online_probe_wgrad`` (stores the gradient) and
+    ``probe_update`` (G = 1, zero weights and momentum, lr 1, no decay, step 0, momentum 0: its
+    Nesterov epilogue returns exactly ``-grad``)."""
+    X, _, _, _, Cp, Fp, Rp = _family_operands(rows, Fd, C)
+    ops = torch.ops.simclr_amd
+    g = torch.Generator().manual_seed(rows + C)
+    dlT = torch.zeros(Cp, Rp, dtype=torch.bfloat16)
+    dlT[:C, :rows] = (0.01 * torch.randn(C, rows, generator=g)).to(torch.bfloat16)
+    dlT, dbp = dlT.to(DEV), torch.randn(rows // 16, Cp, generator=g).to(DEV)
+    grad = torch.full((Cp * Fp + Cp,), 7.0, device=DEV)
+    ops.online_probe_wgrad(X, dlT, dbp, grad, C)
+    W, Mw = torch.zeros(Cp, Fp, device=DEV), torch.zeros(Cp, Fp, device=DEV)
+    b, Mb = torch.zeros(Cp, device=DEV), torch.zeros(Cp, device=DEV)
+    Wsh = torch.zeros(Cp, Fp, device=DEV, dtype=torch.bfloat16)
+    one, zero = torch.ones(1, device=DEV), torch.zeros(1, device=DEV)
+    ops.probe_update(X, torch.arange(rows, device=DEV), dlT, dbp, W, Mw, Wsh, b, Mb, one, zero,
+                     one, 0, 0.0, 1, C)
+    torch.cuda.synchronize()
+    assert torch.equal(W[:C], -grad[:Cp * Fp].view(Cp, Fp)[:C])
+    assert torch.equal(b[:C], -grad[Cp * Fp:][:C])
+    assert float(W.abs().max()) > 0 and float(b.abs().max()) > 0
+    assert not W[C:].any() and not b[C:].any()  # the sweep never moves a padding column
 
 
 # ------------------------------------------------------------------ training path
