@@ -9,6 +9,12 @@
 //   backward  k_bt_grad         G, Gᵀ bf16 from C and the upstream scalar g
 //             k_bt_bwd          dẑ_v = ẑ_other · G(ᵀ) / n (K = D), per-tile column sums of dẑ and dẑ·ẑ
 //             k_bt_std_bwd      dz = rstd · (dẑ − mean_b dẑ − ẑ · mean_b(dẑ·ẑ))
+//   over all ranks (loss.barlow_global), around three collectives:
+//             k_bt_stats, k_bt_merge_standardize  for k_bt_standardize: the same row passes
+//               (bt_row_stats) and the same write pass (bt_write_zhat), the rank merge between
+//             k_bt_slab_merge   Σ_s slab_s alone (bt_slab_sum, as k_bt_loss), for the all-reduce
+//             k_bt_colsum       the tile sums alone (bt_part_sum, as k_bt_std_bwd), for the
+//               all-gather; k_bt_std_bwd then adds the ranks' sums instead of the tiles'
 //
 // No atomics; every sum has a fixed order (rows by row group, splits and tiles by index), so the
 // results are the same bits every run.  n % 32 == 0, D % 64 == 0, 64 <= D <= 2048 (the bindings
@@ -38,23 +44,17 @@ __device__ __forceinline__ float sqrt_rn(float a) { return (float)opaque(sqrt(op
 
 constexpr int BT_RG = 16;  // row groups of the standardisation block (1024 threads)
 
-// grid (D/64, 2 views), 1024 threads: column tx of 64, row group ty of 16.  Two passes over the
-// view's n rows (mean, then centred sum of squares; group ty sums rows ty, ty + 16, ... in order,
-// then the groups are summed in order — the order loss/barlow.py's twin uses, and the mean,
-// the variance and rstd = 1 / sqrt are correctly rounded, so ẑ has the bits of the twin on an
-// IEEE host), a third writes ẑ and, through an LDS tile of 32 rows, its transpose.
+// The two row passes of a (D/64, 2 views) x 1024-thread block: column tx of 64, row group ty of
+// 16; zv = the view's column.  Mean, then centred sum of squares; group ty sums rows ty, ty + 16,
+// ... in order, then the groups are summed in order — the order loss/barlow.py's twin uses, and
+// the mean is correctly rounded, so the statistics have the bits of the twin on an IEEE host.
+// Returns μ in every thread; m2 = Σ_b (z − μ)² (not divided) in the ty == 0 threads only.
 template <typename T>
-__global__ __launch_bounds__(1024) void k_bt_standardize(const T* __restrict__ z, int n, int D,
-                                                         float eps, float* __restrict__ rstd,
-                                                         uint16_t* __restrict__ zh,
-                                                         uint16_t* __restrict__ zhT) {
+__device__ __forceinline__ float bt_row_stats(const T* zv, int n, int D, float& m2) {
 #pragma clang fp contract(off)  // (c · c and the sum round separately, as the twin's do)
   __shared__ float red[BT_RG][64];
-  __shared__ float s_mu[64], s_rs[64];
-  __shared__ uint16_t tile[64][34];  // [column][row of the 32-row chunk]
-  const int v = blockIdx.y, d0 = blockIdx.x * 64;
+  __shared__ float s_mu[64];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const T* zv = z + (size_t)v * n * D + d0 + tx;
   float s = 0.f;
   for (int b = ty; b < n; b += BT_RG) s += ldz(zv + (size_t)b * D);
   red[ty][tx] = s;
@@ -76,21 +76,33 @@ __global__ __launch_bounds__(1024) void k_bt_standardize(const T* __restrict__ z
   if (ty == 0) {
     float t = 0.f;
     for (int k = 0; k < BT_RG; ++k) t += red[k][tx];
-    const float rs = div_rn(1.f, sqrt_rn(div_rn(t, (float)n) + eps));
-    s_rs[tx] = rs;
-    rstd[(size_t)v * D + d0 + tx] = rs;
+    m2 = t;
   }
-  __syncthreads();
-  const float rs = s_rs[tx];
+  return mu;
+}
+
+// rstd = 1 / sqrt(m2 / rows + eps), every step correctly rounded
+__device__ __forceinline__ float bt_rstd(float m2, float rows, float eps) {
+  return div_rn(1.f, sqrt_rn(div_rn(m2, rows) + eps));
+}
+
+// The write pass of the same block: ẑ = (z − μ) · rstd rounded once to bf16, for the view's n
+// rows in chunks of 32, and through an LDS tile its transpose.  A thread's two rows of a chunk are
+// written out and go to the tile as one 32-bit write: inside a helper the compiler no longer
+// pairs them by itself (profiles/barlow_unify.md).
+template <typename T>
+__device__ __forceinline__ void bt_write_zhat(const T* zv, int v, int d0, int n, int D, float mu,
+                                              float rs, uint16_t* __restrict__ zh,
+                                              uint16_t* __restrict__ zhT) {
+  __shared__ __align__(4) uint16_t tile[64][34];  // [column][row of the 32-row chunk]
+  const int tx = threadIdx.x & 63, r = (threadIdx.x >> 6) * 2;  // this thread's rows: r, r + 1
   const int rl = threadIdx.x & 31, tc = threadIdx.x >> 5;  // the transposed write's row, column
   for (int r0 = 0; r0 < n; r0 += 32) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int r = ty * 2 + k;
-      const uint16_t h = f2bf((ldz(zv + (size_t)(r0 + r) * D) - mu) * rs);
-      zh[(size_t)(v * n + r0 + r) * D + d0 + tx] = h;
-      tile[tx][r] = h;
-    }
+    const float x0 = ldz(zv + (size_t)(r0 + r) * D), x1 = ldz(zv + (size_t)(r0 + r + 1) * D);
+    const uint16_t h0 = f2bf((x0 - mu) * rs), h1 = f2bf((x1 - mu) * rs);
+    zh[(size_t)(v * n + r0 + r) * D + d0 + tx] = h0;
+    zh[(size_t)(v * n + r0 + r + 1) * D + d0 + tx] = h1;
+    *(uint32_t*)&tile[tx][r] = (uint32_t)h0 | ((uint32_t)h1 << 16);  // (row stride 68 B, r even)
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
@@ -99,6 +111,47 @@ __global__ __launch_bounds__(1024) void k_bt_standardize(const T* __restrict__ z
     }
     __syncthreads();
   }
+}
+
+// grid (D/64, 2 views), 1024 threads: the row passes, rstd, the write pass
+template <typename T>
+__global__ __launch_bounds__(1024) void k_bt_standardize(const T* __restrict__ z, int n, int D,
+                                                         float eps, float* __restrict__ rstd,
+                                                         uint16_t* __restrict__ zh,
+                                                         uint16_t* __restrict__ zhT) {
+  __shared__ float s_rs[64];
+  const int v = blockIdx.y, d0 = blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const T* zv = z + (size_t)v * n * D + d0 + tx;
+  float m2 = 0.f;  // (set by the ty == 0 threads, read by them alone)
+  const float mu = bt_row_stats(zv, n, D, m2);
+  if (ty == 0) {
+    const float rs = bt_rstd(m2, (float)n, eps);
+    s_rs[tx] = rs;
+    rstd[(size_t)v * D + d0 + tx] = rs;
+  }
+  __syncthreads();
+  bt_write_zhat(zv, v, d0, n, D, mu, s_rs[tx], zh, zhT);
+}
+
+// Σ_{s < splits} slab_s in split order, four consecutive entries (float4 i4 of the D²/4) per thread
+__device__ __forceinline__ float4 bt_slab_sum(const float* part, int splits, int D, size_t i4) {
+  const size_t n4 = (size_t)D * D / 4;
+  const float4* p = (const float4*)part;
+  float4 a = p[i4];
+  for (int s = 1; s < splits; ++s) {
+    const float4 x = p[(size_t)s * n4 + i4];
+    a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w;
+  }
+  return a;
+}
+
+// Σ_{p < parts} src[p · stride] in ascending order from 0.f: the row tiles' (or the ranks') column
+// sums of dẑ and dẑ·ẑ
+__device__ __forceinline__ float bt_part_sum(const float* src, int parts, size_t stride) {
+  float s = 0.f;
+  for (int p = 0; p < parts; ++p) s += src[p * stride];
+  return s;
 }
 
 // grid (D/64, D/64, splits), 4 waves of 32 x 32: slab[z][i][j] = Σ_{b in the slice} ẑ0T[i][b] ẑ1T[j][b]
@@ -156,13 +209,7 @@ __global__ __launch_bounds__(256) void k_bt_loss(const float* __restrict__ part,
                                                  float* __restrict__ lpart) {
   __shared__ float red[4];
   const size_t i4 = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t n4 = (size_t)D * D / 4;
-  const float4* p = (const float4*)part;
-  float4 a = p[i4];
-  for (int s = 1; s < splits; ++s) {
-    const float4 x = p[(size_t)s * n4 + i4];
-    a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w;
-  }
+  float4 a = bt_slab_sum(part, splits, D, i4);
   const float fn = (float)n;
   a.x /= fn; a.y /= fn; a.z /= fn; a.w /= fn;
   ((float4*)C)[i4] = a;
@@ -268,22 +315,24 @@ __global__ __launch_bounds__(256) void k_bt_bwd(const uint16_t* __restrict__ zh,
   }
 }
 
-// grid (D/64, n/32, 2 views): every block sums its 64 columns' tile partials in tile order (the
-// same order in every block), then dz = rstd · ((dẑ − m1) − ẑ · m2) for its 32 rows
+// grid (D/64, n/32, 2 views): every block adds its 64 columns' sums of dẑ and of dẑ·ẑ over the
+// parts of `sums` in ascending order (the same order in every block) and divides by `rows`, then
+// dz = rstd · ((dẑ − m1) − ẑ · m2) for its 32 rows.  sums[v · vstride + p · pstride + which · D + d]:
+//   per rank   colpart [2][n/32][2][D]: parts n/32 (row tiles), pstride 2D, vstride (n/32)·2D, rows n
+//   all ranks  gsum [W][2][2][D]:       parts W (ranks),        pstride 4D, vstride 2D, rows W·n
 __global__ __launch_bounds__(256) void k_bt_std_bwd(const uint16_t* __restrict__ zh,
                                                     const float* __restrict__ rstd,
                                                     const float* __restrict__ dzh,
-                                                    const float* __restrict__ colpart, int n,
+                                                    const float* __restrict__ sums, int parts,
+                                                    int pstride, int vstride, int rows, int n,
                                                     int D, uint16_t* __restrict__ dz_bf16,
                                                     float* __restrict__ dz_f32) {
   __shared__ float m[2][64];
   const int v = blockIdx.z, d0 = blockIdx.x * 64, r0 = blockIdx.y * 32;
-  const int MT = n / 32;
   if (threadIdx.x < 128) {
     const int which = threadIdx.x >> 6, col = threadIdx.x & 63;
-    float s = 0.f;
-    for (int t = 0; t < MT; ++t) s += colpart[((size_t)(v * MT + t) * 2 + which) * D + d0 + col];
-    m[which][col] = s / (float)n;
+    const float* src = sums + (size_t)v * vstride + which * D + d0 + col;
+    m[which][col] = bt_part_sum(src, parts, pstride) / (float)rows;
   }
   __syncthreads();
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
@@ -301,50 +350,27 @@ __global__ __launch_bounds__(256) void k_bt_std_bwd(const uint16_t* __restrict__
 // ---------------------------------------------------------------- the loss over all ranks
 // (loss.barlow_global: W ranks of n rows each, N = W·n; contract: loss/barlow.py.)  Between these
 // launches the ranks exchange [2][2][D] statistics (all-gather), the D x D slab (all-reduce) and
-// [2][2][D] column sums (all-gather); k_bt_corr, k_bt_loss (splits 1, n = N), k_bt_grad and
-// k_bt_bwd serve unchanged.
+// [2][2][D] column sums (all-gather); k_bt_corr, k_bt_loss (splits 1, n = N), k_bt_grad, k_bt_bwd
+// and k_bt_std_bwd (parts = ranks, rows = N) serve unchanged.
 
-// grid (D/64, 2 views), 1024 threads: the two passes of k_bt_standardize, same rows in the same
-// order; stats[0][v][d] = μ_r, stats[1][v][d] = M2_r = Σ_b (z − μ_r)² (not divided)
+// grid (D/64, 2 views), 1024 threads: the row passes alone; stats[0][v][d] = μ_r,
+// stats[1][v][d] = M2_r = Σ_b (z − μ_r)² (not divided)
 template <typename T>
 __global__ __launch_bounds__(1024) void k_bt_stats(const T* __restrict__ z, int n, int D,
                                                    float* __restrict__ stats) {
-#pragma clang fp contract(off)
-  __shared__ float red[BT_RG][64];
-  __shared__ float s_mu[64];
   const int v = blockIdx.y, d0 = blockIdx.x * 64;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const T* zv = z + (size_t)v * n * D + d0 + tx;
-  float s = 0.f;
-  for (int b = ty; b < n; b += BT_RG) s += ldz(zv + (size_t)b * D);
-  red[ty][tx] = s;
-  __syncthreads();
+  float m2 = 0.f;  // (set by the ty == 0 threads, read by them alone)
+  const float mu = bt_row_stats(z + (size_t)v * n * D + d0 + tx, n, D, m2);
   if (ty == 0) {
-    float t = 0.f;
-    for (int k = 0; k < BT_RG; ++k) t += red[k][tx];
-    const float m = div_rn(t, (float)n);
-    s_mu[tx] = m;
-    stats[(size_t)v * D + d0 + tx] = m;
-  }
-  __syncthreads();
-  const float mu = s_mu[tx];
-  s = 0.f;
-  for (int b = ty; b < n; b += BT_RG) {
-    const float c = ldz(zv + (size_t)b * D) - mu;
-    s += c * c;
-  }
-  red[ty][tx] = s;
-  __syncthreads();
-  if (ty == 0) {
-    float t = 0.f;
-    for (int k = 0; k < BT_RG; ++k) t += red[k][tx];
-    stats[(size_t)(2 + v) * D + d0 + tx] = t;
+    stats[(size_t)v * D + d0 + tx] = mu;
+    stats[(size_t)(2 + v) * D + d0 + tx] = m2;
   }
 }
 
 // grid (D/64, 2 views), 1024 threads.  gst [W][2][2][D] are every rank's statistics in rank order:
 // μ = (Σ_r μ_r) / W, M2 = Σ_r (M2_r + n (μ_r − μ)²), both summed in rank order; σ² = M2 / N,
-// rstd as k_bt_standardize's, then its third pass on this rank's rows (ẑ and its transpose).
+// rstd as k_bt_standardize's, then the write pass on this rank's rows.
 // W = 1: μ = μ_0 / 1 and M2 = M2_0 + n · 0, the bits of k_bt_standardize.
 template <typename T>
 __global__ __launch_bounds__(1024) void k_bt_merge_standardize(const T* __restrict__ z,
@@ -353,12 +379,11 @@ __global__ __launch_bounds__(1024) void k_bt_merge_standardize(const T* __restri
                                                                float* __restrict__ rstd,
                                                                uint16_t* __restrict__ zh,
                                                                uint16_t* __restrict__ zhT) {
-#pragma clang fp contract(off)
+#pragma clang fp contract(off)  // (n · d² and the sum round separately, as the twin's do)
   __shared__ float s_mu[64], s_rs[64];
-  __shared__ uint16_t tile[64][34];  // [column][row of the 32-row chunk]
   const int v = blockIdx.y, d0 = blockIdx.x * 64;
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const T* zv = z + (size_t)v * n * D + d0 + tx;
+  const T* zv = z + (size_t)v * n * D + d0 + tx;  // (formed here: after the branch it costs VGPRs)
   if (ty == 0) {
     const size_t rank_stride = (size_t)4 * D;
     const float* pm = gst + (size_t)v * D + d0 + tx;        // μ_r
@@ -373,87 +398,29 @@ __global__ __launch_bounds__(1024) void k_bt_merge_standardize(const T* __restri
       const float t = pq[r * rank_stride] + fn * (d * d);
       m2 = r == 0 ? t : m2 + t;
     }
-    const float fN = (float)((long)W * n);
-    const float rs = div_rn(1.f, sqrt_rn(div_rn(m2, fN) + eps));
+    const float rs = bt_rstd(m2, (float)((long)W * n), eps);
     s_mu[tx] = m;
     s_rs[tx] = rs;
     rstd[(size_t)v * D + d0 + tx] = rs;
   }
   __syncthreads();
-  const float mu = s_mu[tx];
-  const float rs = s_rs[tx];
-  const int rl = threadIdx.x & 31, tc = threadIdx.x >> 5;  // the transposed write's row, column
-  for (int r0 = 0; r0 < n; r0 += 32) {
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int r = ty * 2 + k;
-      const uint16_t h = f2bf((ldz(zv + (size_t)(r0 + r) * D) - mu) * rs);
-      zh[(size_t)(v * n + r0 + r) * D + d0 + tx] = h;
-      tile[tx][r] = h;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-      const int c = tc + 32 * k;
-      zhT[((size_t)v * D + d0 + c) * n + r0 + rl] = tile[c][rl];
-    }
-    __syncthreads();
-  }
+  bt_write_zhat(zv, v, d0, n, D, s_mu[tx], s_rs[tx], zh, zhT);
 }
 
 // four consecutive entries per thread, as k_bt_loss: S = Σ_s slab_s in split order (not divided)
 __global__ __launch_bounds__(256) void k_bt_slab_merge(const float* __restrict__ part, int splits,
                                                        int D, float* __restrict__ S) {
   const size_t i4 = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t n4 = (size_t)D * D / 4;
-  const float4* p = (const float4*)part;
-  float4 a = p[i4];
-  for (int s = 1; s < splits; ++s) {
-    const float4 x = p[(size_t)s * n4 + i4];
-    a.x += x.x; a.y += x.y; a.z += x.z; a.w += x.w;
-  }
-  ((float4*)S)[i4] = a;
+  ((float4*)S)[i4] = bt_slab_sum(part, splits, D, i4);
 }
 
 // one thread per (view, dẑ | dẑ·ẑ, column), 4 D of them (a multiple of 256): the row tiles'
-// partials of k_bt_bwd in tile order, as k_bt_std_bwd sums them; csum [2][2][D]
+// partials of k_bt_bwd in tile order, as k_bt_std_bwd sums them per rank; csum [2][2][D]
 __global__ __launch_bounds__(256) void k_bt_colsum(const float* __restrict__ colpart, int MT, int D,
                                                    float* __restrict__ csum) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const int col = i % D, which = (i / D) & 1, v = i / (2 * D);
-  float s = 0.f;
-  for (int t = 0; t < MT; ++t) s += colpart[((size_t)(v * MT + t) * 2 + which) * D + col];
-  csum[i] = s;
-}
-
-// grid (D/64, n/32, 2 views): k_bt_std_bwd with the means over all N rows: every block adds its
-// 64 columns' sums of the W ranks (gsum [W][2][2][D]) in rank order and divides by N
-__global__ __launch_bounds__(256) void k_bt_std_bwd_global(const uint16_t* __restrict__ zh,
-                                                           const float* __restrict__ rstd,
-                                                           const float* __restrict__ dzh,
-                                                           const float* __restrict__ gsum, int W,
-                                                           int n, int D,
-                                                           uint16_t* __restrict__ dz_bf16,
-                                                           float* __restrict__ dz_f32) {
-  __shared__ float m[2][64];
-  const int v = blockIdx.z, d0 = blockIdx.x * 64, r0 = blockIdx.y * 32;
-  if (threadIdx.x < 128) {
-    const int which = threadIdx.x >> 6, col = threadIdx.x & 63;
-    float s = 0.f;
-    for (int r = 0; r < W; ++r) s += gsum[((size_t)(r * 2 + v) * 2 + which) * D + d0 + col];
-    m[which][col] = s / (float)((long)W * n);
-  }
-  __syncthreads();
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const float m1 = m[0][tx], m2 = m[1][tx];
-  const float rs = rstd[(size_t)v * D + d0 + tx];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const size_t i = (size_t)(v * n + r0 + ty * 8 + k) * D + d0 + tx;
-    const float val = rs * ((dzh[i] - m1) - bf2f(zh[i]) * m2);
-    if (dz_bf16) dz_bf16[i] = f2bf(val);
-    if (dz_f32) dz_f32[i] = val;
-  }
+  csum[i] = bt_part_sum(colpart + ((size_t)v * MT * 2 + which) * D + col, MT, (size_t)2 * D);
 }
 
 }  // namespace
@@ -514,12 +481,19 @@ void barlow_backward(const uint16_t* zh, const uint16_t* G, const uint16_t* GT, 
   HIP_CHECK_LAUNCH();
 }
 
+// the one std-backward launch; the two layouts of `sums` are at k_bt_std_bwd
+static void std_backward(const uint16_t* zh, const float* rstd, const float* dzh, const float* sums,
+                         int parts, int pstride, int vstride, int rows, int n, int D,
+                         uint16_t* dz_bf16, float* dz_f32, hipStream_t s) {
+  hipLaunchKernelGGL(k_bt_std_bwd, dim3(D / 64, n / 32, 2), dim3(256), 0, s, zh, rstd, dzh, sums,
+                     parts, pstride, vstride, rows, n, D, dz_bf16, dz_f32);
+  HIP_CHECK_LAUNCH();
+}
+
 void barlow_std_backward(const uint16_t* zh, const float* rstd, const float* dzh,
                          const float* colpart, int n, int D, uint16_t* dz_bf16, float* dz_f32,
                          hipStream_t s) {
-  hipLaunchKernelGGL(k_bt_std_bwd, dim3(D / 64, n / 32, 2), dim3(256), 0, s, zh, rstd, dzh,
-                     colpart, n, D, dz_bf16, dz_f32);
-  HIP_CHECK_LAUNCH();
+  std_backward(zh, rstd, dzh, colpart, n / 32, 2 * D, (n / 32) * 2 * D, n, n, D, dz_bf16, dz_f32, s);
 }
 
 // ---- the loss over all ranks (W ranks, N = W · n rows)
@@ -559,7 +533,5 @@ void barlow_colsum(const float* colpart, int n, int D, float* csum, hipStream_t 
 void barlow_std_backward_global(const uint16_t* zh, const float* rstd, const float* dzh,
                                 const float* gsum, int W, int n, int D, uint16_t* dz_bf16,
                                 float* dz_f32, hipStream_t s) {
-  hipLaunchKernelGGL(k_bt_std_bwd_global, dim3(D / 64, n / 32, 2), dim3(256), 0, s, zh, rstd, dzh,
-                     gsum, W, n, D, dz_bf16, dz_f32);
-  HIP_CHECK_LAUNCH();
+  std_backward(zh, rstd, dzh, gsum, W, 4 * D, 2 * D, W * n, n, D, dz_bf16, dz_f32, s);
 }

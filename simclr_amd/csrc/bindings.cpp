@@ -1052,14 +1052,32 @@ void check_bt(int64_t n, int64_t D) {
   TORCH_CHECK(D >= 64 && D <= 2048 && D % 64 == 0, "barlow: D must be a multiple of 64 in "
               "[64, 2048], got ", D);
 }
-void bt_standardize(const Tensor& z, double eps, const Tensor& rstd, const Tensor& zh,
-                    const Tensor& zhT) {
-  TORCH_CHECK(z.dim() == 2 && z.size(0) % 2 == 0, "bt_standardize: z must be [2n][D]");
-  const int64_t n = z.size(0) / 2, D = z.size(1);
-  check_bt(n, D);
+void check_bt_z(const Tensor& z, const char* what) {
+  TORCH_CHECK(z.dim() == 2 && z.size(0) % 2 == 0, what, ": z must be [2n][D]");
+  check_bt(z.size(0) / 2, z.size(1));
   TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
                   (z.scalar_type() == at::kBFloat16 || z.scalar_type() == at::kFloat),
-              "bt_standardize: z must be a contiguous bf16 or fp32 GPU tensor");
+              what, ": z must be a contiguous bf16 or fp32 GPU tensor");
+}
+// (bf() checks the dtype, the device and the layout where the pointer is taken)
+void check_bt_zh(const Tensor& zh, const char* what) {
+  TORCH_CHECK(zh.dim() == 2 && zh.size(0) % 2 == 0, what, ": zh must be [2n][D]");
+  check_bt(zh.size(0) / 2, zh.size(1));
+}
+// exactly one of dz_bf16 / dz_f32, of `numel` elements -> (bf16, fp32) pointers, one of them null
+std::pair<uint16_t*, float*> bt_dz(const c10::optional<Tensor>& dz_bf16,
+                                   const c10::optional<Tensor>& dz_f32, int64_t numel,
+                                   const char* what) {
+  uint16_t* ob = optbfw(dz_bf16, "dz_bf16");
+  float* of = optf32w(dz_f32, "dz_f32");
+  TORCH_CHECK((ob != nullptr) != (of != nullptr), what, ": one of dz_bf16 / dz_f32");
+  TORCH_CHECK((ob ? dz_bf16->numel() : dz_f32->numel()) == numel, what, ": dz size");
+  return {ob, of};
+}
+void bt_standardize(const Tensor& z, double eps, const Tensor& rstd, const Tensor& zh,
+                    const Tensor& zhT) {
+  check_bt_z(z, "bt_standardize");
+  const int64_t n = z.size(0) / 2, D = z.size(1);
   TORCH_CHECK(eps > 0.0, "bt_standardize: eps must be > 0");
   TORCH_CHECK(rstd.numel() == 2 * D && zh.numel() == 2 * n * D && zhT.numel() == 2 * n * D,
               "bt_standardize sizes");
@@ -1103,9 +1121,8 @@ void bt_grad(const Tensor& C, double lambd, const Tensor& gout, const Tensor& G,
 }
 void bt_backward(const Tensor& zh, const Tensor& G, const Tensor& GT, const Tensor& dzh,
                  const Tensor& colpart) {
-  TORCH_CHECK(zh.dim() == 2 && zh.size(0) % 2 == 0, "bt_backward: zh must be [2n][D]");
+  check_bt_zh(zh, "bt_backward");
   const int64_t n = zh.size(0) / 2, D = zh.size(1);
-  check_bt(n, D);
   TORCH_CHECK(G.numel() == D * D && GT.numel() == D * D && dzh.numel() == 2 * n * D &&
                   colpart.numel() == 2 * (n / 32) * 2 * D, "bt_backward sizes");
   barlow_backward(bf(zh, "zh"), bf(G, "G"), bf(GT, "GT"), (int)n, (int)D, f32w(dzh, "dzh"),
@@ -1114,29 +1131,24 @@ void bt_backward(const Tensor& zh, const Tensor& G, const Tensor& GT, const Tens
 void bt_std_backward(const Tensor& zh, const Tensor& rstd, const Tensor& dzh,
                      const Tensor& colpart, const c10::optional<Tensor>& dz_bf16,
                      const c10::optional<Tensor>& dz_f32) {
-  TORCH_CHECK(zh.dim() == 2 && zh.size(0) % 2 == 0, "bt_std_backward: zh must be [2n][D]");
+  check_bt_zh(zh, "bt_std_backward");
   const int64_t n = zh.size(0) / 2, D = zh.size(1);
-  check_bt(n, D);
   TORCH_CHECK(rstd.numel() == 2 * D && dzh.numel() == 2 * n * D &&
                   colpart.numel() == 2 * (n / 32) * 2 * D, "bt_std_backward sizes");
-  uint16_t* ob = optbfw(dz_bf16, "dz_bf16");
-  float* of = optf32w(dz_f32, "dz_f32");
-  TORCH_CHECK((ob != nullptr) != (of != nullptr), "bt_std_backward: one of dz_bf16 / dz_f32");
-  TORCH_CHECK((ob ? dz_bf16->numel() : dz_f32->numel()) == 2 * n * D, "bt_std_backward: dz size");
+  const auto dz = bt_dz(dz_bf16, dz_f32, 2 * n * D, "bt_std_backward");
   barlow_std_backward(bf(zh, "zh"), f32(rstd, "rstd"), f32(dzh, "dzh"), f32(colpart, "colpart"),
-                      (int)n, (int)D, ob, of, cur_stream());
+                      (int)n, (int)D, dz.first, dz.second, cur_stream());
 }
-// the loss over W ranks (loss.barlow_global): W is the leading size of the gathered tensors
-void check_bt_world(int64_t W, int64_t n, const char* what) {
+// the loss over W ranks (loss.barlow_global): W is the leading size of the gathered tensors,
+// g = gstats or gsum [W][2][2][D] -> W
+int64_t check_bt_gathered(const Tensor& g, int64_t n, int64_t D, const char* what,
+                          const char* name) {
+  TORCH_CHECK(g.dim() == 4 && g.size(1) == 2 && g.size(2) == 2 && g.size(3) == D, what, ": ", name,
+              " must be [W][2][2][D] with D = ", D);
+  const int64_t W = g.size(0);
   TORCH_CHECK(W >= 1 && W <= 1024 && W * n <= (1 << 20), what, ": W ranks of n rows need "
               "1 <= W <= 1024 and W * n <= 2^20, got W ", W, ", n ", n);
-}
-void check_bt_z(const Tensor& z, const char* what) {
-  TORCH_CHECK(z.dim() == 2 && z.size(0) % 2 == 0, what, ": z must be [2n][D]");
-  check_bt(z.size(0) / 2, z.size(1));
-  TORCH_CHECK(z.is_cuda() && z.is_contiguous() &&
-                  (z.scalar_type() == at::kBFloat16 || z.scalar_type() == at::kFloat),
-              what, ": z must be a contiguous bf16 or fp32 GPU tensor");
+  return W;
 }
 void bt_stats(const Tensor& z, const Tensor& stats) {
   check_bt_z(z, "bt_stats");
@@ -1150,11 +1162,7 @@ void bt_merge_standardize(const Tensor& z, const Tensor& gstats, double eps, con
                           const Tensor& zh, const Tensor& zhT) {
   check_bt_z(z, "bt_merge_standardize");
   const int64_t n = z.size(0) / 2, D = z.size(1);
-  TORCH_CHECK(gstats.dim() == 4 && gstats.size(1) == 2 && gstats.size(2) == 2 &&
-                  gstats.size(3) == D,
-              "bt_merge_standardize: gstats must be [W][2][2][D] with D = ", D);
-  const int64_t W = gstats.size(0);
-  check_bt_world(W, n, "bt_merge_standardize");
+  const int64_t W = check_bt_gathered(gstats, n, D, "bt_merge_standardize", "gstats");
   TORCH_CHECK(eps > 0.0, "bt_merge_standardize: eps must be > 0");
   TORCH_CHECK(rstd.numel() == 2 * D && zh.numel() == 2 * n * D && zhT.numel() == 2 * n * D,
               "bt_merge_standardize sizes: rstd [2][D], zh [2n][D], zhT [2][D][n]");
@@ -1182,23 +1190,14 @@ void bt_colsum(const Tensor& colpart, const Tensor& csum) {
 void bt_std_backward_global(const Tensor& zh, const Tensor& rstd, const Tensor& dzh,
                             const Tensor& gsum, const c10::optional<Tensor>& dz_bf16,
                             const c10::optional<Tensor>& dz_f32) {
-  TORCH_CHECK(zh.dim() == 2 && zh.size(0) % 2 == 0, "bt_std_backward_global: zh must be [2n][D]");
+  check_bt_zh(zh, "bt_std_backward_global");
   const int64_t n = zh.size(0) / 2, D = zh.size(1);
-  check_bt(n, D);
-  TORCH_CHECK(gsum.dim() == 4 && gsum.size(1) == 2 && gsum.size(2) == 2 && gsum.size(3) == D,
-              "bt_std_backward_global: gsum must be [W][2][2][D] with D = ", D);
-  const int64_t W = gsum.size(0);
-  check_bt_world(W, n, "bt_std_backward_global");
+  const int64_t W = check_bt_gathered(gsum, n, D, "bt_std_backward_global", "gsum");
   TORCH_CHECK(rstd.numel() == 2 * D && dzh.numel() == 2 * n * D,
               "bt_std_backward_global sizes: rstd [2][D], dzh [2n][D]");
-  uint16_t* ob = optbfw(dz_bf16, "dz_bf16");
-  float* of = optf32w(dz_f32, "dz_f32");
-  TORCH_CHECK((ob != nullptr) != (of != nullptr),
-              "bt_std_backward_global: one of dz_bf16 / dz_f32");
-  TORCH_CHECK((ob ? dz_bf16->numel() : dz_f32->numel()) == 2 * n * D,
-              "bt_std_backward_global: dz size");
+  const auto dz = bt_dz(dz_bf16, dz_f32, 2 * n * D, "bt_std_backward_global");
   barlow_std_backward_global(bf(zh, "zh"), f32(rstd, "rstd"), f32(dzh, "dzh"), f32(gsum, "gsum"),
-                             (int)W, (int)n, (int)D, ob, of, cur_stream());
+                             (int)W, (int)n, (int)D, dz.first, dz.second, cur_stream());
 }
 
 // ------------------------------------------------------------------------------- lars

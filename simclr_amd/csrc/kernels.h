@@ -258,13 +258,15 @@ void barlow_grad(const float* C, int D, float lambd, const float* gout, uint16_t
 // dzh fp32 [2n][D], colpart [2][n/32][2][D] (per row tile: column sums of dzh and of dzh·zh)
 void barlow_backward(const uint16_t* zh, const uint16_t* G, const uint16_t* GT, int n, int D,
                      float* dzh, float* colpart, hipStream_t s);
+// dz (bf16 or fp32, the other null) from dzh and the column means: colpart's tiles added in order, / n
 void barlow_std_backward(const uint16_t* zh, const float* rstd, const float* dzh,
                          const float* colpart, int n, int D, uint16_t* dz_bf16, float* dz_f32,
                          hipStream_t s);
 // the loss over W ranks of n rows each (loss.barlow_global), around three collectives:
 // stats [2][2][D] = (μ_r, M2_r) per view; gstats [W][2][2][D] the all-gathered ones, merged in
 // rank order into rstd, zh, zhT; S [D][D] = Σ part in split order (undivided, to be all-reduced);
-// csum [2][2][D] = colpart summed in tile order; gsum [W][2][2][D] the all-gathered ones
+// csum [2][2][D] = colpart summed in tile order; gsum [W][2][2][D] the all-gathered ones, which
+// barlow_std_backward_global (the kernel of barlow_std_backward) adds in rank order, / (W·n)
 void barlow_stats(const void* z, int z_f32, int n, int D, float* stats, hipStream_t s);
 void barlow_merge_standardize(const void* z, int z_f32, const float* gstats, int W, int n, int D,
                               float eps, float* rstd, uint16_t* zh, uint16_t* zhT, hipStream_t s);

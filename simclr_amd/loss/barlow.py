@@ -158,44 +158,26 @@ def _loss_terms(C: torch.Tensor, lambd: float) -> torch.Tensor:
 
 
 class _BarlowTwinFn(torch.autograd.Function):
-    """The twin with ``round_operands``: ẑ and G rounded to bf16 at the kernels' points."""
+    """The twin with ``round_operands``: ẑ and G rounded to bf16 at the kernels' points, with the
+    three exchanges of the contract (statistics, the slab, the column sums) where the kernels
+    have them.  With no group and ``W`` = 1 (the per-rank loss) the exchanges are the identity:
+    μ = μ_0 / 1 and M2 = M2_0 + n · 0, a gather of one block, no all-reduce."""
 
     @staticmethod
-    def forward(ctx, z, n, lambd, eps):
-        zh, rstd = _standardize(z.float(), n, eps)
-        zh = _bf16_round(zh)
-        C = zh[0].t() @ zh[1] / n
-        ctx.save_for_backward(zh, rstd, C)
-        ctx.cfg = (n, lambd, z.dtype)
-        ctx.mark_non_differentiable(C)
-        return _loss_terms(C, lambd), C
-
-    @staticmethod
-    def backward(ctx, gout, _gc):
-        zh, rstd, C = ctx.saved_tensors
-        n, lambd, zdtype = ctx.cfg
-        g = gout.float()
-        eye = torch.eye(C.shape[0], dtype=torch.bool, device=C.device)
-        G = _bf16_round(torch.where(eye, (-2.0 * g) * (1.0 - C), (2.0 * g * lambd) * C))
-        dzh = torch.stack([zh[1] @ G.t(), zh[0] @ G]) / n
-        m1 = dzh.sum(dim=1, keepdim=True) / n
-        m2 = (dzh * zh).sum(dim=1, keepdim=True) / n
-        dz = rstd * ((dzh - m1) - zh * m2)
-        return dz.reshape(2 * n, -1).to(zdtype), None, None, None
-
-
-class _BarlowGlobalTwinFn(torch.autograd.Function):
-    """The rounded twin over all ranks: :class:`_BarlowTwinFn` with the three exchanges of the
-    contract (statistics, the slab, the column sums) at the kernels' points."""
+    def _exchange(x, W, group):
+        """[W][*x.shape] in rank order; the per-rank loss (no group, W = 1) has the one block."""
+        return x.unsqueeze(0) if group is None and W == 1 else _gather(x, W, group)
 
     @staticmethod
     def forward(ctx, z, n, lambd, eps, group, W):
         zf = z.float()
-        gst = _gather(_local_stats(zf, n), W, group)
+        gst = _BarlowTwinFn._exchange(_local_stats(zf, n), W, group)
         mu, rstd = _merge_stats(gst, n, eps)
         zh = _bf16_round((zf.view(2, n, -1) - mu) * rstd)
-        S = (zh[0].t() @ zh[1]).contiguous()
-        dist.all_reduce(S, group=group)
+        S = zh[0].t() @ zh[1]
+        if group is not None or W > 1:
+            S = S.contiguous()
+            dist.all_reduce(S, group=group)
         C = S / (W * n)
         ctx.save_for_backward(zh, rstd, C)
         ctx.cfg = (n, lambd, z.dtype, group, W)
@@ -211,7 +193,7 @@ class _BarlowGlobalTwinFn(torch.autograd.Function):
         G = _bf16_round(torch.where(eye, (-2.0 * g) * (1.0 - C), (2.0 * g * lambd) * C))
         dzh = torch.stack([zh[1] @ G.t(), zh[0] @ G]) / n
         csum = torch.stack([dzh.sum(dim=1), (dzh * zh).sum(dim=1)], dim=1)  # [2 views][2][D]
-        tot = _rank_sum(_gather(csum, W, group))
+        tot = _rank_sum(_BarlowTwinFn._exchange(csum, W, group))
         m1 = tot[:, 0:1] / (W * n)
         m2 = tot[:, 1:2] / (W * n)
         dz = rstd * ((dzh - m1) - zh * m2)
@@ -253,14 +235,10 @@ def barlow_twins_torch(z: torch.Tensor, n: int, lambd: float, eps: float = 1e-5,
     ranks (all-gather, all-reduce), so nothing here depends on it."""
     if z.dim() != 2 or z.shape[0] != 2 * n:
         raise ValueError(f"z must be [2n][D] with n = {n}, got {tuple(z.shape)}")
-    if group is not None or world_size > 1:
-        if round_operands:
-            loss, C = _BarlowGlobalTwinFn.apply(z, n, float(lambd), float(eps), group,
-                                                int(world_size))
-        else:
-            loss, C = _global_plain(z, n, float(lambd), float(eps), group, int(world_size))
-    elif round_operands:
-        loss, C = _BarlowTwinFn.apply(z, n, float(lambd), float(eps))
+    if round_operands:
+        loss, C = _BarlowTwinFn.apply(z, n, float(lambd), float(eps), group, int(world_size))
+    elif group is not None or world_size > 1:
+        loss, C = _global_plain(z, n, float(lambd), float(eps), group, int(world_size))
     else:
         zh, _ = _standardize(z if z.dtype == torch.float64 else z.float(), n, eps)
         C = zh[0].t() @ zh[1] / n
@@ -269,60 +247,10 @@ def barlow_twins_torch(z: torch.Tensor, n: int, lambd: float, eps: float = 1e-5,
 
 
 class _BarlowHipFn(torch.autograd.Function):
-    """Seven launches: standardise, correlate, loss partials, their sum; G, dẑ, dz."""
-
-    @staticmethod
-    def forward(ctx, z, n, lambd, eps):
-        from ..ops import _ext
-        ops = _ext.ops()
-        D = z.shape[1]
-        dev = z.device
-        zc = z.contiguous()
-        rstd = torch.empty((2, D), device=dev, dtype=torch.float32)
-        zh = torch.empty((2 * n, D), device=dev, dtype=torch.bfloat16)
-        zhT = torch.empty((2, D, n), device=dev, dtype=torch.bfloat16)
-        ops.bt_standardize(zc, eps, rstd, zh, zhT)
-        splits = ops.bt_corr_splits(n, D)
-        part = torch.empty((splits, D, D), device=dev, dtype=torch.float32)
-        ops.bt_corr(zhT, n, splits, part)
-        C = torch.empty((D, D), device=dev, dtype=torch.float32)
-        lpart = torch.empty((ops.bt_loss_blocks(D),), device=dev, dtype=torch.float32)
-        ops.bt_loss(part, splits, n, lambd, C, lpart)
-        out = torch.empty((1,), device=dev, dtype=torch.float32)
-        ops.nt_reduce_loss(lpart, 1.0, out)
-        ctx.save_for_backward(zh, rstd, C)
-        ctx.cfg = (n, lambd, z.dtype)
-        ctx.mark_non_differentiable(C)
-        return out.view(()), C
-
-    @staticmethod
-    def backward(ctx, gout, _gc):
-        from ..ops import _ext
-        ops = _ext.ops()
-        zh, rstd, C = ctx.saved_tensors
-        n, lambd, zdtype = ctx.cfg
-        D = zh.shape[1]
-        dev = zh.device
-        g = gout.reshape(1).float().contiguous()
-        G = torch.empty((D, D), device=dev, dtype=torch.bfloat16)
-        GT = torch.empty((D, D), device=dev, dtype=torch.bfloat16)
-        ops.bt_grad(C, lambd, g, G, GT)
-        dzh = torch.empty((2 * n, D), device=dev, dtype=torch.float32)
-        colpart = torch.empty((2, n // 32, 2, D), device=dev, dtype=torch.float32)
-        ops.bt_backward(zh, G, GT, dzh, colpart)
-        if zdtype == torch.bfloat16:
-            dz = torch.empty((2 * n, D), device=dev, dtype=torch.bfloat16)
-            ops.bt_std_backward(zh, rstd, dzh, colpart, dz, None)
-        else:
-            dz = torch.empty((2 * n, D), device=dev, dtype=torch.float32)
-            ops.bt_std_backward(zh, rstd, dzh, colpart, None, dz)
-        return dz, None, None, None
-
-
-class _BarlowGlobalHipFn(torch.autograd.Function):
-    """The loss over all ranks: ten launches (nine with a single slab; the per-rank path has
-    seven: stats + merge replace standardise, the slab merge is new, colsum + the global std
-    backward replace the std backward) and three collectives on the current stream
+    """``st`` None, the per-rank loss: seven launches (standardise, correlate, loss partials,
+    their sum; G, dẑ, dz).  ``st`` a parallel state, the loss over all ranks: ten launches (nine
+    with a single slab: stats + merge replace standardise, the slab merge is new, colsum + the
+    global std backward replace the std backward) and three collectives on the current stream
     (statistics all-gather, slab all-reduce, column-sum all-gather); ``bt_corr``, ``bt_loss``
     (one slab, n = N), ``bt_grad`` and ``bt_backward`` are the per-rank path's."""
 
@@ -332,28 +260,35 @@ class _BarlowGlobalHipFn(torch.autograd.Function):
         ops = _ext.ops()
         D = z.shape[1]
         dev = z.device
-        W = st.world_size
         zc = z.contiguous()
-        stats = torch.empty((2, 2, D), device=dev, dtype=torch.float32)
-        ops.bt_stats(zc, stats)
-        gstats = torch.empty((W, 2, 2, D), device=dev, dtype=torch.float32)
-        dist.all_gather_into_tensor(gstats.view(-1), stats.view(-1), group=st.group)
+        if st is not None:
+            W = st.world_size
+            stats = torch.empty((2, 2, D), device=dev, dtype=torch.float32)
+            ops.bt_stats(zc, stats)
+            gstats = torch.empty((W, 2, 2, D), device=dev, dtype=torch.float32)
+            dist.all_gather_into_tensor(gstats.view(-1), stats.view(-1), group=st.group)
         rstd = torch.empty((2, D), device=dev, dtype=torch.float32)
         zh = torch.empty((2 * n, D), device=dev, dtype=torch.bfloat16)
         zhT = torch.empty((2, D, n), device=dev, dtype=torch.bfloat16)
-        ops.bt_merge_standardize(zc, gstats, eps, rstd, zh, zhT)
+        if st is None:
+            ops.bt_standardize(zc, eps, rstd, zh, zhT)
+        else:
+            ops.bt_merge_standardize(zc, gstats, eps, rstd, zh, zhT)
         splits = ops.bt_corr_splits(n, D)
         part = torch.empty((splits, D, D), device=dev, dtype=torch.float32)
         ops.bt_corr(zhT, n, splits, part)
-        if splits > 1:
-            S = torch.empty((D, D), device=dev, dtype=torch.float32)
-            ops.bt_slab_merge(part, splits, S)
-        else:
-            S = part.view(D, D)  # (the single slab is S_r already)
-        dist.all_reduce(S, group=st.group)
+        rows = n
+        if st is not None:
+            if splits > 1:
+                S = torch.empty((D, D), device=dev, dtype=torch.float32)
+                ops.bt_slab_merge(part, splits, S)
+            else:
+                S = part.view(D, D)  # (the single slab is S_r already)
+            dist.all_reduce(S, group=st.group)
+            part, splits, rows = S, 1, W * n
         C = torch.empty((D, D), device=dev, dtype=torch.float32)
         lpart = torch.empty((ops.bt_loss_blocks(D),), device=dev, dtype=torch.float32)
-        ops.bt_loss(S, 1, W * n, lambd, C, lpart)
+        ops.bt_loss(part, splits, rows, lambd, C, lpart)
         out = torch.empty((1,), device=dev, dtype=torch.float32)
         ops.nt_reduce_loss(lpart, 1.0, out)
         ctx.save_for_backward(zh, rstd, C)
@@ -369,7 +304,6 @@ class _BarlowGlobalHipFn(torch.autograd.Function):
         n, lambd, zdtype, st = ctx.cfg
         D = zh.shape[1]
         dev = zh.device
-        W = st.world_size
         g = gout.reshape(1).float().contiguous()
         G = torch.empty((D, D), device=dev, dtype=torch.bfloat16)
         GT = torch.empty((D, D), device=dev, dtype=torch.bfloat16)
@@ -377,16 +311,16 @@ class _BarlowGlobalHipFn(torch.autograd.Function):
         dzh = torch.empty((2 * n, D), device=dev, dtype=torch.float32)
         colpart = torch.empty((2, n // 32, 2, D), device=dev, dtype=torch.float32)
         ops.bt_backward(zh, G, GT, dzh, colpart)
-        csum = torch.empty((2, 2, D), device=dev, dtype=torch.float32)
-        ops.bt_colsum(colpart, csum)
-        gsum = torch.empty((W, 2, 2, D), device=dev, dtype=torch.float32)
-        dist.all_gather_into_tensor(gsum.view(-1), csum.view(-1), group=st.group)
-        if zdtype == torch.bfloat16:
-            dz = torch.empty((2 * n, D), device=dev, dtype=torch.bfloat16)
-            ops.bt_std_backward_global(zh, rstd, dzh, gsum, dz, None)
-        else:
-            dz = torch.empty((2 * n, D), device=dev, dtype=torch.float32)
-            ops.bt_std_backward_global(zh, rstd, dzh, gsum, None, dz)
+        sums, std_backward = colpart, ops.bt_std_backward
+        if st is not None:
+            csum = torch.empty((2, 2, D), device=dev, dtype=torch.float32)
+            ops.bt_colsum(colpart, csum)
+            gsum = torch.empty((st.world_size, 2, 2, D), device=dev, dtype=torch.float32)
+            dist.all_gather_into_tensor(gsum.view(-1), csum.view(-1), group=st.group)
+            sums, std_backward = gsum, ops.bt_std_backward_global
+        bf16 = zdtype == torch.bfloat16
+        dz = torch.empty((2 * n, D), device=dev, dtype=torch.bfloat16 if bf16 else torch.float32)
+        std_backward(zh, rstd, dzh, sums, *((dz, None) if bf16 else (None, dz)))
         return dz, None, None, None, None
 
 
@@ -425,13 +359,10 @@ class BarlowTwins(nn.Module):
         if z.dim() != 2 or z.shape[0] != 2 * n:
             raise ValueError(f"z must be [2n][D], got {tuple(z.shape)}")
         st = pstate.get()
-        if self.global_batch and st.comm:
-            if hip_path(z, n):
-                loss, C = _BarlowGlobalHipFn.apply(z, n, self.lambd, self.eps, st)
-                return (loss, C) if return_c else loss
-            return barlow_twins_torch(z, n, self.lambd, self.eps, return_c=return_c,
-                                      group=st.group, world_size=st.world_size, rank=st.rank)
+        st = st if self.global_batch and st.comm else None  # the all-rank loss or the per-rank one
         if hip_path(z, n):
-            loss, C = _BarlowHipFn.apply(z, n, self.lambd, self.eps)
+            loss, C = _BarlowHipFn.apply(z, n, self.lambd, self.eps, st)
             return (loss, C) if return_c else loss
-        return barlow_twins_torch(z, n, self.lambd, self.eps, return_c=return_c)
+        group, W, rank = (None, 1, 0) if st is None else (st.group, st.world_size, st.rank)
+        return barlow_twins_torch(z, n, self.lambd, self.eps, return_c=return_c, group=group,
+                                  world_size=W, rank=rank)

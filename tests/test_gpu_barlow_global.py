@@ -1,6 +1,6 @@
 """The kernels of ``loss.barlow_global`` (csrc/barlow.hip: k_bt_stats, k_bt_merge_standardize,
-k_bt_slab_merge, k_bt_colsum, k_bt_std_bwd_global around the per-rank k_bt_corr / k_bt_loss /
-k_bt_grad / k_bt_bwd) against the rounded torch twin over W ranks, in ONE process: the
+k_bt_slab_merge, k_bt_colsum around the per-rank k_bt_corr / k_bt_loss / k_bt_grad / k_bt_bwd /
+k_bt_std_bwd) against the rounded torch twin over W ranks, in ONE process: the
 collectives of loss/barlow.py are in-process fakes in the manner of
 tests/test_gpu_ntxent_gather.py.  The peers' blocks of every exchange are filled from passes of
 the twin over every rank's z (three exchanges: three passes, each making one more exchange right);
@@ -176,6 +176,78 @@ def test_statistics_and_zhat_have_the_twins_bits(monkeypatch, W, n, D, r):
     assert torch.equal(rstd.cpu(), rs.squeeze(1))
     assert torch.equal(zh.cpu().view(2, n, D), zt)
     assert torch.equal(zhT.cpu(), zt.transpose(1, 2))
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32])
+@pytest.mark.parametrize("n,D", [(32, 64), (96, 128)])
+def test_standardize_is_stats_then_merge_of_one_rank(n, D, dtype):
+    """``bt_standardize`` against ``bt_stats`` + ``bt_merge_standardize`` on the one rank's
+    statistics: rstd, ẑ and ẑᵀ bit for bit (the kernels share the row passes and the write pass).
+    (32, 64) is the smallest legal shape; n = 96 has 6 rows per row group and 3 chunks of the
+    write pass.  Column 5 of view 0 is constant."""
+    from simclr_amd.ops import _ext
+    ops = _ext.ops()
+    z = views(n, D, seed_for(n, D))
+    z[:n, 5] = 1.25
+    z = (z.to(torch.bfloat16) if dtype == torch.bfloat16 else z * 1.0009765625).to(DEV)
+
+    def outputs():
+        return (torch.empty(2, D, device=DEV),
+                torch.empty(2 * n, D, device=DEV, dtype=torch.bfloat16),
+                torch.empty(2, D, n, device=DEV, dtype=torch.bfloat16))
+
+    one, two = outputs(), outputs()
+    ops.bt_standardize(z, 1e-5, *one)
+    stats = torch.empty(2, 2, D, device=DEV)
+    ops.bt_stats(z, stats)
+    ops.bt_merge_standardize(z, stats[None], 1e-5, *two)
+    assert bool((one[1].view(2, n, D)[0, :, 5] == 0).all())
+    for a, b, what in zip(one, two, ("rstd", "zh", "zhT")):
+        assert torch.equal(a, b), what
+
+
+def test_std_backward_reads_tiles_view_major_and_ranks_rank_major():
+    """n = 64, D = 64, W = 2: ``colpart`` [2 views][2 tiles][2][D] and ``gsum`` [2 ranks][2 views]
+    [2][D] have one shape and two meanings, and the two ops run one kernel with two sets of
+    strides.  Both ops on the SAME buffer, each against dz = rstd·((dẑ − m1) − ẑ·m2) on the host
+    with the parts added in ascending order in fp32 and m = Σ / 64 (tiles) or Σ / 128 (ranks).
+    Bound per element: 8 · 2^-24 · rstd · (|dẑ| + |m1| + |ẑ·m2|): four fp32 roundings in the
+    expression, fused product or not, and one ulp for each of the GPU's two divisions, doubled.
+    A swapped stride moves m1 and m2 by about |Σ| / 64, some 1e-2: four orders above the bound."""
+    from simclr_amd.ops import _ext
+    ops = _ext.ops()
+    n, D, W = 64, 64, 2
+    g = torch.Generator().manual_seed(64064)
+    dzh = torch.randn(2 * n, D, generator=g)
+    rstd = torch.rand(2, D, generator=g) + 0.5
+    zh = torch.randn(2 * n, D, generator=g).to(torch.bfloat16)
+    sums = torch.randn(2, 2, 2, D, generator=g)
+    assert sums.unique().numel() == sums.numel()
+
+    def host(part, rows):
+        """part(p, v) -> [2][D] = (Σ dẑ, Σ dẑ·ẑ) of part p for view v"""
+        want, bound = [], []
+        for v in range(2):
+            tot = torch.zeros(2, D)
+            for p in range(2):
+                tot = tot + part(p, v)
+            m1, m2 = (tot / rows).double()
+            d, h = dzh[v * n:(v + 1) * n].double(), zh[v * n:(v + 1) * n].double()
+            rs = rstd[v].double()
+            want.append(rs * ((d - m1) - h * m2))
+            bound.append(8 * 2.0 ** -24 * rs * (d.abs() + m1.abs() + (h * m2).abs()))
+        return torch.cat(want), torch.cat(bound)
+
+    got = []
+    for op, part, rows in ((ops.bt_std_backward, lambda t, v: sums[v, t], n),
+                           (ops.bt_std_backward_global, lambda r, v: sums[r, v], W * n)):
+        dz = torch.empty(2 * n, D, device=DEV)
+        op(zh.to(DEV), rstd.to(DEV), dzh.to(DEV), sums.to(DEV), None, dz)
+        want, bound = host(part, float(rows))
+        err = (dz.cpu().double() - want).abs()
+        assert bool((err <= bound).all()), float((err / bound).max())
+        got.append(dz.cpu())
+    assert not torch.equal(got[0], got[1])  # (both ops reading one layout would pass the above)
 
 
 @pytest.mark.parametrize("W,n,D", [(2, 32, 64), (4, 32, 128), (2, 96, 128), (2, 64, 2048)])
