@@ -1,8 +1,9 @@
 """Downstream evaluation entry point (reference: /root/reference/eval.py).
 
-    python eval.py experiment.target_dir=PATH [parameter.classifier={centroid,knn,kmeans,linear,nonlinear}]
+    python eval.py experiment.target_dir=PATH [parameter.classifier={centroid,knn,kmeans,geometry,linear,nonlinear}]
                    [parameter.knn_k=200] [parameter.knn_t=0.1]
                    [parameter.kmeans_k=null] [parameter.kmeans_restarts=8] [parameter.kmeans_iters=50]
+                   [+parameter.geometry_t=2.0]
                    [parameter.use_full_encoder=true]
 """
 from simclr_amd.config import hydra_main

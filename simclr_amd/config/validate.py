@@ -161,6 +161,8 @@ def check_eval_conf(cfg) -> None:
         _check(t is None or t > 0.0, "parameter.knn_t must be > 0")
     if p.get("classifier") == "kmeans":
         _check_kmeans(cfg)
+    if p.get("classifier") == "geometry":
+        _check_geometry(cfg)
 
 
 def _check_kmeans(cfg) -> None:
@@ -176,6 +178,20 @@ def _check_kmeans(cfg) -> None:
     R, T = p.get("kmeans_restarts"), p.get("kmeans_iters")
     try:
         kmeans.check_limits(K, 8 if R is None else R, 50 if T is None else T)
+    except ValueError as err:
+        raise AssertionError("parameter." + str(err)) from None
+
+
+def _check_geometry(cfg) -> None:
+    """The geometry probe's one key ``parameter.geometry_t`` (the uniformity temperature, a finite
+    number > 0; ``ops.geometry.check_limits``); nothing is swept."""
+    from ..ops import geometry
+    p = cfg["parameter"]
+    _check(p.get("sweep_lr") is None and p.get("sweep_decay") is None,
+           "parameter.sweep_lr / parameter.sweep_decay need parameter.classifier=linear")
+    t = p.get("geometry_t")
+    try:
+        geometry.check_limits(t=t)
     except ValueError as err:
         raise AssertionError("parameter." + str(err)) from None
 

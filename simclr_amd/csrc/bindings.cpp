@@ -1569,6 +1569,65 @@ void kmeans_fit_op(const Tensor& xn, const Tensor& cmat, int64_t K, int64_t R, i
   km_objective(sp, g.R, g.N, J.data_ptr<double>(), st);
 }
 
+// ------------------------------------------------------------------------------- geometry probe
+// rows N and padded width Dp of either half, checked before any launch
+void geo_check_shape(const char* op, int64_t N, int64_t Dp) {
+  TORCH_CHECK(N >= 2, op, ": N must be >= 2, got ", N);
+  TORCH_CHECK(Dp >= geo_kstep() && Dp % geo_kstep() == 0 && Dp <= geo_max_dp(), op,
+              ": Dp must be a multiple of ", geo_kstep(), " and <= ", geo_max_dp(), ", got ", Dp);
+  TORCH_CHECK(N * Dp < (1ll << 31), op, ": N * Dp must be < 2^31, got N ", N, " Dp ", Dp);
+}
+
+void geometry_pair_op(const Tensor& xn, const c10::optional<Tensor>& labels, double t,
+                      const Tensor& fpart, const Tensor& ipart) {
+  TORCH_CHECK(xn.dim() == 2, "geometry_pair: xn [N][Dp]");
+  const int64_t N = xn.size(0), Dp = xn.size(1);
+  geo_check_shape("geometry_pair", N, Dp);
+  TORCH_CHECK(N <= 128 * 65535, "geometry_pair: N must be <= ", 128 * 65535,
+              " (the tile count of the triangle stays below 2^31), got ", N);
+  TORCH_CHECK(t > 0.0 && std::isfinite(t), "geometry_pair: t must be > 0 and finite, got ", t);
+  const int* lab = nullptr;
+  if (labels.has_value() && labels->defined()) {
+    check_dev(*labels, at::kInt, "labels");
+    TORCH_CHECK(labels->numel() == N, "geometry_pair: labels must be [N]");
+    lab = labels->data_ptr<int>();
+  }
+  const int64_t tiles = geo_pair_tiles((int)N);
+  check_dev(ipart, at::kInt, "ipart");
+  TORCH_CHECK(fpart.numel() == tiles * 3 && ipart.numel() == tiles * 2,
+              "geometry_pair: fpart must be [", tiles, "][3] and ipart [", tiles, "][2]");
+  geo_pair(bf(xn, "xn"), lab, (int)N, (int)Dp, (float)(2.0 * t), f32w(fpart, "fpart"),
+           ipart.data_ptr<int>(), cur_stream());
+}
+
+void geometry_center_op(const Tensor& x, const Tensor& mu, const Tensor& cT) {
+  TORCH_CHECK(x.dim() == 2 && cT.dim() == 2, "geometry_center: x [N][D], cT [Dp][Np]");
+  const int64_t N = x.size(0), D = x.size(1), Dp = cT.size(0), Np = cT.size(1);
+  const int64_t ks = geo_kstep();
+  TORCH_CHECK(D >= 1 && Dp == (D + ks - 1) / ks * ks && Np == (N + 63) / 64 * 64,
+              "geometry_center: cT must be [D rounded up to ", ks, "][N rounded up to 64], got [",
+              Dp, "][", Np, "] for N ", N, " D ", D);
+  geo_check_shape("geometry_center", N, Dp);
+  TORCH_CHECK(mu.numel() == Dp, "geometry_center: mu must be [Dp]");
+  const int64_t chunks = (N + geo_chunk() - 1) / geo_chunk();
+  at::Tensor csum = at::empty({chunks * Dp}, x.options().dtype(at::kDouble));
+  geo_center(f32(x, "x"), (int)N, (int)D, (int)Dp, (int)Np, csum.data_ptr<double>(),
+             f32w(mu, "mu"), bfw(cT, "cT"), cur_stream());
+}
+
+void geometry_syrk_op(const Tensor& cT, int64_t N, const Tensor& S) {
+  TORCH_CHECK(cT.dim() == 2, "geometry_syrk: cT [Dp][Np]");
+  const int64_t Dp = cT.size(0), Np = cT.size(1);
+  geo_check_shape("geometry_syrk", N, Dp);
+  TORCH_CHECK(Np == (N + 63) / 64 * 64, "geometry_syrk: cT must be [Dp][N rounded up to 64]");
+  check_dev(S, at::kDouble, "S");
+  TORCH_CHECK(S.dim() == 2 && S.size(0) == Dp && S.size(1) == Dp, "geometry_syrk: S must be [Dp][Dp]");
+  const int64_t slab_n = (int64_t)geo_syrk_splits((int)N, (int)Dp) * geo_syrk_tiles((int)Dp) * 4096;
+  at::Tensor slab = at::empty({slab_n}, S.options());
+  geo_syrk(bf(cT, "cT"), (int)N, (int)Dp, (int)Np, slab.data_ptr<double>(), S.data_ptr<double>(),
+           cur_stream());
+}
+
 // ------------------------------------------------------------------------------- linear probes
 // What the sweep and the online probe check alike: features [.][Fp] (bf16, contiguous: bf() checks
 // where the pointer is taken) with Fp a multiple of the kernels' K step; returns Cp = 16 ceil(C / 16)
@@ -1834,6 +1893,12 @@ TORCH_LIBRARY(simclr_amd, m) {
   m.def("kmeans_assign(Tensor xn, Tensor cmat, int K, int R, Tensor(a!) a, Tensor(b!) s, Tensor(c!) counts, Tensor(d!) changed, Tensor it) -> ()", &kmeans_assign_op);
   m.def("kmeans_update(Tensor xn, Tensor a, int K, int R, Tensor(a!) counts, Tensor(b!) cmat, Tensor(c!)? S, Tensor(d!) it) -> ()", &kmeans_update_op);
   m.def("kmeans_fit(Tensor xn, Tensor(a!) cmat, int K, int R, int T, Tensor(b!) a, Tensor(c!) s, Tensor(d!) counts, Tensor(e!) changed, Tensor(f!) J) -> ()", &kmeans_fit_op);
+  m.def("geometry_pair(Tensor xn, Tensor? labels, float t, Tensor(a!) fpart, Tensor(b!) ipart) -> ()", &geometry_pair_op);
+  m.def("geometry_pair_tiles(int N) -> int", [](int64_t N) -> int64_t { return geo_pair_tiles((int)N); });
+  m.def("geometry_pair_chain() -> int", []() -> int64_t { return geo_pair_chain(); });
+  m.def("geometry_center(Tensor x, Tensor(a!) mu, Tensor(b!) cT) -> ()", &geometry_center_op);
+  m.def("geometry_syrk(Tensor cT, int N, Tensor(a!) S) -> ()", &geometry_syrk_op);
+  m.def("geometry_syrk_splits(int N, int Dp) -> int", [](int64_t N, int64_t Dp) -> int64_t { return geo_syrk_splits((int)N, (int)Dp); });
   m.def("maxpool_fwd(Tensor x, Tensor(a!) y, Tensor(b!) arg, int K, int S, int P) -> ()", &maxpool_fwd_op);
   m.def("maxpool_bwd(Tensor dy, Tensor arg, Tensor(a!) dx, int K, int S, int P) -> ()", &maxpool_bwd_op);
   m.def("stem_s2d(Tensor img, int creal, int P, Tensor(a!) xs) -> ()", &stem_s2d_op);

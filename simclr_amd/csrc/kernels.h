@@ -373,6 +373,25 @@ void km_update(const uint16_t* X, const int* a, int N, int Fp, int K, int Kp, in
                uint16_t* C, float* S, float* slab, int* it, hipStream_t st);
 void km_objective(const float* s, int R, int N, double* J, hipStream_t st);
 
+// ---- geometry.hip: geometry probe (pair statistics of the Gram matrix's upper triangle consumed
+// in registers; centred features, their second-moment matrix by its upper triangle)
+int geo_kstep();       // Dp is D rounded up to this
+int geo_max_dp();
+int geo_chunk();       // rows per fp32 accumulation chunk of the second-moment product
+int geo_pair_chain();  // the longest fp32 chain of roundings in a pair tile's sums
+long long geo_pair_tiles(int N);      // 128 x 128 tiles on or above the diagonal
+int geo_syrk_tiles(int Dp);           // 64 x 64 tiles on or above the diagonal
+int geo_syrk_splits(int N, int Dp);   // splits of the chunks over blocks
+// Xn [N][Dp] bf16, labels [N] or null; fpart [tiles][3] = (E, A, A_same), ipart [tiles][2] =
+// (pairs, same pairs) per tile; c2t = 2 t
+void geo_pair(const uint16_t* Xn, const int* labels, int N, int Dp, float c2t, float* fpart,
+              int* ipart, hipStream_t s);
+// x [N][D] fp32 -> mu [Dp], cT [Dp][Np] bf16 (Np = N rounded up to 64); csum [chunks][Dp] scratch
+void geo_center(const float* x, int N, int D, int Dp, int Np, double* csum, float* mu,
+                uint16_t* cT, hipStream_t s);
+// S [Dp][Dp] fp64 = c^T c; slab [splits][tiles][64][64] fp64 scratch
+void geo_syrk(const uint16_t* cT, int N, int Dp, int Np, double* slab, double* S, hipStream_t s);
+
 // ---- probe.hip: linear-probe sweep (G classifiers on one feature batch: fused forward / CE /
 // gradient, fused weight gradient / Nesterov SGD update)
 int probe_kstep();        // Fp is F rounded up to this

@@ -7,6 +7,9 @@ Parity: ``centroid_eval`` (``/root/reference/eval.py:61-85``), ``learnable_eval`
 * knn: the weighted k-nearest-neighbour classifier of Wu et al. (InstDisc), not in the reference:
   cosine neighbours in the train features, votes ``exp((sim - 1) / T)``; the train numbers are
   leave-one-out (``ops/knn.py`` holds the contract);
+* kmeans / geometry: the label-free probes of ``ops/kmeans.py`` (spherical k-means scored against
+  the labels) and ``ops/geometry.py`` (uniformity, alignment and the covariance spectrum), not in
+  the reference; neither trains anything;
 * linear / nonlinear: SGD(lr = lr·batches/256, momentum, **nesterov=True**, wd = decay),
   ``CosineAnnealingLR(T_max = epochs·ceil(N/batches))`` stepped every batch, shuffled batches;
   after every epoch train and val (top-1, top-k, mean CE) are recomputed; the JSON reports the
@@ -32,7 +35,7 @@ import torch.nn.functional as F
 
 from ..models.heads import CentroidClassifier, LinearClassifier, NonLinearClassifier
 from ..ops.classify import ce_rank, cross_entropy
-from ..ops import kmeans, probe_sweep
+from ..ops import geometry, kmeans, probe_sweep
 from ..ops.knn import knn_topk, knn_vote
 from ..utils.misc import cfg_get
 from ..optim.schedule import cosine_lr
@@ -129,6 +132,34 @@ def kmeans_eval(cfg, train: DownstreamDataset, val: DownstreamDataset, num_class
         "iterations": kmeans.iterations(fit.changed),
         "cluster_sizes": [int(c) for c in fit.counts[b].tolist()],
     })
+    return out
+
+
+@torch.no_grad()
+def geometry_eval(cfg, train: DownstreamDataset, val: DownstreamDataset) -> Dict:
+    """Uniformity / alignment and the covariance spectrum of the train and the val features
+    (``ops/geometry.py`` holds the contract).  Nothing is trained and ``parameter.top_k`` is not
+    used.  The metrics carry a ``train_`` / ``val_`` prefix, as do ``rows`` and ``nonfinite`` (the
+    count of non-finite feature values: with any, the split's metrics may be NaN)."""
+    t = cfg_get(cfg, "parameter.geometry_t", 2.0)
+    try:
+        geometry.check_limits(t=t)
+    except ValueError as err:
+        raise ValueError("parameter." + str(err)) from None
+    if sweep_values(cfg) is not None:
+        raise ValueError("parameter.sweep_lr / parameter.sweep_decay need parameter.classifier=linear")
+    dev = train.data.device
+    out = {"geometry_t": float(t), "dims": int(train.data.shape[1])}
+    for name, ds in (("train", train), ("val", val)):
+        x = ds.data.to(dev)
+        sums = geometry.pair_stats(x, ds.targets, float(t))
+        spec = geometry.spectrum(x)
+        m = dict(geometry.pair_metrics(sums), **geometry.spectrum_metrics(spec.eig, spec.cov_diag))
+        m["rows"] = int(x.shape[0])
+        m["nonfinite"] = int((~torch.isfinite(x)).sum())
+        logging.info("{} uniformity: {}, alignment: {}, effective rank: {}".format(
+            name, m["uniformity"], m["class_alignment"], m["effective_rank"]))
+        out.update({name + "_" + k: v for k, v in m.items()})
     return out
 
 
@@ -314,6 +345,8 @@ def run_probe(cfg, kind: str, train: DownstreamDataset, val: DownstreamDataset, 
         }
     if kind == "kmeans":
         return kmeans_eval(cfg, train, val, num_classes)
+    if kind == "geometry":
+        return geometry_eval(cfg, train, val)
     F_ = train.data.shape[1]
     if kind == "linear":
         clf = LinearClassifier(F_, num_classes).to(device)
@@ -321,7 +354,7 @@ def run_probe(cfg, kind: str, train: DownstreamDataset, val: DownstreamDataset, 
         clf = NonLinearClassifier(F_, num_classes).to(device)
     else:
         raise ValueError(f"unknown classifier {kind!r} "
-                         "(centroid | knn | kmeans | linear | nonlinear)")
+                         "(centroid | knn | kmeans | geometry | linear | nonlinear)")
     sv = sweep_values(cfg)
     if sv is not None:
         if kind != "linear":

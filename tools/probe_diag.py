@@ -27,19 +27,18 @@ sys.path.insert(0, str(ROOT))
 
 
 def stats(X: torch.Tensor) -> dict:
+    from simclr_amd.ops import geometry
     X = X.float()
     finite = torch.isfinite(X)
     Xf = torch.where(finite, X, torch.zeros_like(X))
     nrm = Xf.norm(dim=1)
     sd = Xf.std(dim=0)
-    Xc = (Xf - Xf.mean(0, keepdim=True)).double()
-    sv = torch.linalg.svdvals(Xc[: min(20000, Xc.shape[0])])
-    p = sv ** 2 / (sv ** 2).sum().clamp_min(1e-30)
-    ent = -(p * torch.log(p.clamp_min(1e-30))).sum()
+    # the covariance spectrum of all rows (ops/geometry.py); None when there is no variance at all
+    geo = geometry.spectrum_metrics(*geometry.spectrum(Xf)[:2])
     return {"row_norm_mean": float(nrm.mean()), "row_norm_max": float(nrm.max()),
             "nonfinite": int((~finite).sum()), "dim_std_min": float(sd.min()),
             "dim_std_median": float(sd.median()), "dim_std_max": float(sd.max()),
-            "effective_rank": float(torch.exp(ent)), "top_sv_share": float(p[0]),
+            "effective_rank": geo["effective_rank"], "top_sv_share": geo["top_eig_share"],
             "dims": int(X.shape[1])}
 
 
