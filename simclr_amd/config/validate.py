@@ -34,6 +34,33 @@ def _check_supervised(cfg) -> None:
            "loss.supervised=true is not available with loss.gather=ring")
 
 
+def _check_negatives(cfg) -> None:
+    """The opt-in weighted negatives of NT-Xent (loss/ntxent.py): ``loss.hard_beta`` >= 0,
+    ``loss.tau_plus`` in [0, 1), ``loss.decoupled`` a boolean.  A loss with any of them off its
+    default is NT-Xent's only: not with ``loss.kind`` barlow / nnclr, ``loss.supervised`` or the
+    ring (``loss.gather=true`` is fine)."""
+    import math
+    loss = (cfg.get("loss") if hasattr(cfg, "get") else None) or {}
+    beta, tau_plus, dec = loss.get("hard_beta"), loss.get("tau_plus"), loss.get("decoupled")
+    for key, v in (("loss.hard_beta", beta), ("loss.tau_plus", tau_plus)):
+        if v is not None:
+            _check(isinstance(v, (int, float)) and not isinstance(v, bool),
+                   f"{key} must be a number")
+            _check(math.isfinite(v), f"{key} must be finite")
+    _check(beta is None or beta >= 0, "loss.hard_beta must be >= 0")
+    _check(tau_plus is None or 0 <= tau_plus < 1, "loss.tau_plus must be in [0, 1)")
+    _check(dec is None or isinstance(dec, bool), "loss.decoupled must be a boolean")
+    on = [k for k, v in (("loss.hard_beta", beta), ("loss.tau_plus", tau_plus),
+                         ("loss.decoupled", dec)) if v]
+    if not on:
+        return
+    kind = loss.get("kind")
+    _check(kind in (None, "ntxent"), f"{on[0]} is not available with loss.kind={kind}")
+    _check(not loss.get("supervised"), f"{on[0]} is not available with loss.supervised=true")
+    _check(str(loss.get("gather")).lower() != "ring",
+           f"{on[0]} is not available with loss.gather=ring")
+
+
 LOSS_KINDS = ("ntxent", "barlow", "nnclr")
 NN_QUEUE_DEFAULT = 16384
 NN_QUEUE_MULTIPLE, NN_QUEUE_MAX = 256, 131072
@@ -104,6 +131,7 @@ def check_pretrain_conf(cfg) -> None:
     _check_blur(cfg)
     _check_supervised(cfg)
     _check_loss_kind(cfg)
+    _check_negatives(cfg)
     _check_online_probe(cfg)
     _check(p["temperature"] > 0.0, "parameter.temperature must be > 0")
     _check(p["epochs"] > 0, "parameter.epochs must be > 0")

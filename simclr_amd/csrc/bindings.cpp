@@ -10,6 +10,7 @@
 #include <torch/library.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "kernels.h"
@@ -867,6 +868,71 @@ void nt_normalize_backward(const Tensor& zn, const Tensor& inv_norm, const Tenso
 void nt_reduce_loss(const Tensor& loss_rows, double scale, const Tensor& out) {
   ntxent_reduce_loss(f32(loss_rows, "loss_rows"), loss_rows.numel(), (float)scale, f32w(out, "out"),
                      cur_stream());
+}
+// ---- weighted negatives (loss.hard_beta / loss.tau_plus / loss.decoupled): part holds 5 floats
+// per row and split if hard_beta > 0, else 3; stats [R][4] = (L1, A, B, L0) per row
+void check_nt_weighted(const char* op, double hard_beta, double tau_plus) {
+  TORCH_CHECK(std::isfinite(hard_beta) && hard_beta >= 0.0, op,
+              ": hard_beta must be a finite number >= 0, got ", hard_beta);
+  TORCH_CHECK(std::isfinite(tau_plus) && tau_plus >= 0.0 && tau_plus < 1.0, op,
+              ": tau_plus must be in [0, 1), got ", tau_plus);
+}
+void nt_w_forward_range(const Tensor& znT, int64_t R, int64_t col_offset, int64_t n_local,
+                        double inv_temp, double hard_beta, const Tensor& part, int64_t c_lo,
+                        int64_t c_hi, int64_t splits, int64_t split_base) {
+  TORCH_CHECK(znT.dim() == 2, "nt_w_forward_range: znT must be [D][Ccols]");
+  const int D = znT.size(0), Ccols = znT.size(1);
+  check_nt(R, Ccols, D, col_offset, n_local);
+  check_nt_weighted("nt_w_forward_range", hard_beta, 0.0);
+  const int64_t np = hard_beta > 0.0 ? 5 : 3;
+  TORCH_CHECK(c_lo >= 0 && c_lo < c_hi && c_hi <= Ccols && c_lo % 16 == 0 && c_hi % 16 == 0 &&
+                  splits >= 1 && split_base >= 0,
+              "nt_w_forward_range: column window / splits");
+  TORCH_CHECK(part.numel() >= (split_base + splits) * R * np,
+              "nt_w_forward_range: part must hold (split_base + splits) * R * ", np, " floats, got ",
+              part.numel());
+  ntxent_weighted_forward_range(f32(znT, "znT"), R, Ccols, D, col_offset, n_local, (float)inv_temp,
+                                (float)hard_beta, f32w(part, "part"), c_lo, c_hi, splits,
+                                split_base, cur_stream());
+}
+void nt_w_finish(const Tensor& part, int64_t R, int64_t splits, int64_t Ccols, double inv_temp,
+                 double hard_beta, double tau_plus, bool decoupled, const Tensor& stats,
+                 const Tensor& loss) {
+  check_nt_weighted("nt_w_finish", hard_beta, tau_plus);
+  const int64_t np = hard_beta > 0.0 ? 5 : 3;
+  TORCH_CHECK(R >= 1 && splits >= 1 && Ccols >= R && Ccols % 16 == 0 && Ccols < (1LL << 24),
+              "nt_w_finish: R / splits / Ccols");
+  TORCH_CHECK(part.numel() >= splits * R * np, "nt_w_finish: part must hold splits * R * ", np,
+              " floats, got ", part.numel());
+  TORCH_CHECK(stats.numel() == R * 4, "nt_w_finish: stats must hold R * 4 floats, got ",
+              stats.numel());
+  TORCH_CHECK(((uintptr_t)stats.data_ptr() & 15) == 0, "nt_w_finish: stats must be 16-byte aligned");
+  TORCH_CHECK(loss.numel() == R, "nt_w_finish: loss must hold R floats, got ", loss.numel());
+  ntxent_weighted_finish(f32(part, "part"), R, splits, Ccols, (float)inv_temp, (float)hard_beta,
+                         (float)tau_plus, decoupled ? 1 : 0, f32w(stats, "stats"),
+                         f32w(loss, "loss"), cur_stream());
+}
+void nt_w_backward_part(bool row_mode, const Tensor& zn, const Tensor& znT, const Tensor& stats,
+                        int64_t R, int64_t col_offset, int64_t n_local, double inv_temp,
+                        double hard_beta, double gscale, const c10::optional<Tensor>& gout,
+                        const Tensor& part, int64_t splits, const Tensor& out) {
+  TORCH_CHECK(znT.dim() == 2, "nt_w_backward: znT must be [D][Ccols]");
+  const int D = znT.size(0), Ccols = znT.size(1);
+  check_nt(R, Ccols, D, col_offset, n_local);
+  check_nt_weighted("nt_w_backward", hard_beta, 0.0);
+  TORCH_CHECK(zn.numel() == (int64_t)Ccols * D, "nt_w_backward: zn size");
+  TORCH_CHECK(stats.numel() == R * 4, "nt_w_backward: stats must hold R * 4 floats, got ",
+              stats.numel());
+  TORCH_CHECK(((uintptr_t)stats.data_ptr() & 15) == 0,
+              "nt_w_backward: stats must be 16-byte aligned");
+  const int64_t nown = row_mode ? R : Ccols;
+  TORCH_CHECK(splits >= 1 && part.numel() >= splits * nown * D && out.numel() == nown * D,
+              "nt_w_backward sizes");
+  ntxent_weighted_backward_part(row_mode ? 1 : 0, f32(zn, "zn"), f32(znT, "znT"),
+                                f32(stats, "stats"), R, Ccols, D, col_offset, n_local,
+                                (float)inv_temp, (float)hard_beta, (float)gscale,
+                                optf32(gout, "gout"), f32w(part, "part"), splits, f32w(out, "out"),
+                                cur_stream());
 }
 // ---- label mode (SupCon): ycol = the columns' int32 labels
 // ycol covers the columns [y0, y0 + len): the scored window and the rank's own rows lie inside
@@ -1971,6 +2037,9 @@ TORCH_LIBRARY(simclr_amd, m) {
   m.def("nt_backward_part(bool row_mode, Tensor zn, Tensor znT, Tensor lse, int R, int col_offset, int n_local, float inv_temp, float gscale, Tensor? gout, Tensor(a!) part, int splits, Tensor(b!) out) -> ()", &nt_backward_part);
   m.def("nt_normalize_backward(Tensor zn, Tensor inv_norm, Tensor dzn, Tensor(a!)? dz_bf16, Tensor(b!)? dz_f32) -> ()", &nt_normalize_backward);
   m.def("nt_reduce_loss(Tensor loss_rows, float scale, Tensor(a!) out) -> ()", &nt_reduce_loss);
+  m.def("nt_w_forward_range(Tensor znT, int R, int col_offset, int n_local, float inv_temp, float hard_beta, Tensor(a!) part, int c_lo, int c_hi, int splits, int split_base) -> ()", &nt_w_forward_range);
+  m.def("nt_w_finish(Tensor part, int R, int splits, int Ccols, float inv_temp, float hard_beta, float tau_plus, bool decoupled, Tensor(a!) stats, Tensor(b!) loss) -> ()", &nt_w_finish);
+  m.def("nt_w_backward_part(bool row_mode, Tensor zn, Tensor znT, Tensor stats, int R, int col_offset, int n_local, float inv_temp, float hard_beta, float gscale, Tensor? gout, Tensor(a!) part, int splits, Tensor(b!) out) -> ()", &nt_w_backward_part);
   m.def("nt_sup_forward_range(Tensor znT, Tensor ycol, int y0, int R, int col_offset, int n_local, float inv_temp, Tensor(a!) part, int c_lo, int c_hi, int splits, int split_base) -> ()", &nt_sup_forward_range);
   m.def("nt_sup_finish(Tensor part, int R, int splits, Tensor(a!) lse, Tensor(b!) inv_cnt, Tensor(c!) loss) -> ()", &nt_sup_finish);
   m.def("nt_sup_backward_part(bool row_mode, Tensor zn, Tensor znT, Tensor lse, Tensor inv_cnt, Tensor ycol, int R, int col_offset, int n_local, float inv_temp, float gscale, Tensor? gout, Tensor(a!) part, int splits, Tensor(b!) out) -> ()", &nt_sup_backward_part);

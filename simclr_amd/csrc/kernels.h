@@ -236,6 +236,20 @@ void supcon_backward_part(int row_mode, const float* zn, const float* znT, const
                           const float* inv_cnt, const int* ycol, int R, int Ccols, int D,
                           int col_offset, float inv_temp, float gscale, const float* gout,
                           float* part, int splits, float* out, hipStream_t s);
+// weighted negatives (hard-negative beta >= 0, debiased 0 <= tau_plus < 1, decoupled): the
+// positive leaves the sums; part holds 5 floats per row if beta > 0, else 3; stats [R][4] =
+// (L1, A, B, L0) per row, written by the finish and read by the backward passes
+void ntxent_weighted_forward_range(const float* znT, int R, int Ccols, int D, int col_offset,
+                                   int n_local, float inv_temp, float beta, float* part, int c_lo,
+                                   int c_hi, int splits, int split_base, hipStream_t s);
+void ntxent_weighted_finish(const float* part, int R, int splits, int Ccols, float inv_temp,
+                            float beta, float tau_plus, int decoupled, float* stats, float* loss,
+                            hipStream_t s);
+void ntxent_weighted_backward_part(int row_mode, const float* zn, const float* znT,
+                                   const float* stats, int R, int Ccols, int D, int col_offset,
+                                   int n_local, float inv_temp, float beta, float gscale,
+                                   const float* gout, float* part, int splits, float* out,
+                                   hipStream_t s);
 // out[v*n + i] = labels[idx ? idx[i] : i] (int32 or int64 labels, n_src of them), v < views
 void supcon_expand_labels(const void* labels, int labels_i64, const int64_t* idx, long n_src,
                           int n, int views, int* out, hipStream_t s);

@@ -178,16 +178,66 @@ struct LabelRule {
   __device__ __forceinline__ float pos_weight(int r) const { return inv_cnt[r]; }
 };
 
+// ---------------------------------------------------------------- negative rules
+// How the other columns enter an anchor's denominator is a compile-time "negative rule", the
+// second axis of the same kernels.
+//   plain    (NT-Xent, SupCon): every column but the anchor's own, the positives included, in one
+//            log-sum-exp; backward weight exp(s − lse).  This is the code as it was: the rule has
+//            no state and no kernel argument, and the kernels branch on it with `if constexpr`.
+//   weighted (pair rule only; hard-negative / debiased / decoupled NT-Xent, loss/ntxent.py): the
+//            positive is kept out of the sums and carried as s_ip; L1 = LSE_Neg (1+β)s and, for
+//            HARD (β > 0), L0 = LSE_Neg βs in a second online log-sum-exp of the same helpers
+//            (HARD = false: L0 = log N, no second sum, no second exp, no argument).  Forward
+//            partial part[split][r][3 or 5] = (m1, l1, s_ip or -inf[, m0, l0]).  The finish kernel
+//            evaluates the shifted form per row and leaves stats[r] = (L1, A, B, L0); backward
+//            weight A·((1+β)·exp((1+β)s − L1) − β·exp(βs − L0)) at a negative, B at the positive.
+struct PlainNeg {
+  static constexpr bool WEIGHTED = false;
+  static constexpr int NX = 0;  // floats per row of a forward partial beyond Pos::NP
+};
+
+template <bool HARD_>
+struct WeightedNeg {
+  static constexpr bool WEIGHTED = true, HARD = HARD_;
+  static constexpr int NX = HARD ? 2 : 0;
+  const float beta, beta1;  // β, 1 + β
+  float m0 = -INFINITY, l0 = 0.f;
+  // the kernels' trailing arguments: β for HARD, none otherwise
+  __device__ __forceinline__ WeightedNeg() : beta(0.f), beta1(1.f) {}
+  __device__ __forceinline__ explicit WeightedNeg(float beta) : beta(beta), beta1(1.f + beta) {}
+  __device__ __forceinline__ void push(float& m, float& l, float v) {
+    if (HARD) {
+      lse_push(m, l, beta1 * v);
+      lse_push(m0, l0, beta * v);
+    } else {
+      lse_push(m, l, v);
+    }
+  }
+  __device__ __forceinline__ void merge_lanes(int off) {
+    if (HARD) lse_merge_lanes(m0, l0, off);
+  }
+  __device__ __forceinline__ void store(float* p) const {
+    if (HARD) p[0] = m0, p[1] = l0;
+  }
+  // dS_ia / (g·A_i) at a negative with logit v, st = (L1, A, B, L0) of the anchor
+  __device__ __forceinline__ float neg_weight(float v, const float4& st) const {
+    if (HARD) return beta1 * __expf(beta1 * v - st.x) - beta * __expf(beta * v - st.w);
+    return __expf(v - st.x);
+  }
+};
+
 // Forward: grid (R/16, splits), one wave per block. Owned = anchor rows [r0, r0+16) (local),
-// partners = columns [c_beg, c_end). Writes part[split][r][Pos::NP], self excluded.  ycol / y0
-// are the label rule's (the window and the owned rows lie inside), n_local the pair rule's.
-template <int D, class Rule>
+// partners = columns [c_beg, c_end). Writes part[split][r][Pos::NP + Neg::NX], self excluded.
+// ycol / y0 are the label rule's (the window and the owned rows lie inside), n_local the pair
+// rule's, neg_args the negative rule's (none for the plain rule).
+template <int D, class Rule, class Neg = PlainNeg, class... NegArgs>
 __global__ __launch_bounds__(64) void k_ntxent_fwd(const float* __restrict__ znT,
                                                      int R, int Ccols, int col_offset,
                                                      int n_local, float inv_temp,
                                                      int cols_per_split, float* __restrict__ part,
                                                      int c_lo, int c_hi, int split_base,
-                                                     const int* __restrict__ ycol, int y0) {
+                                                     const int* __restrict__ ycol, int y0,
+                                                     NegArgs... neg_args) {
   const int lane = threadIdx.x;
   const int g = lane >> 4, li = lane & 15;
   const int r0 = blockIdx.x * 16;
@@ -203,6 +253,7 @@ __global__ __launch_bounds__(64) void k_ntxent_fwd(const float* __restrict__ znT
   const int self_c = col_offset + my_r;
   Rule rule(ycol, y0, nullptr, n_local, col_offset, self_c);
   typename Rule::Pos pos;
+  [[maybe_unused]] Neg neg{neg_args...};
   float m = -INFINITY, l = 0.f;
   for (int q0 = c_beg; q0 < c_end; q0 += 16) {
     const f32x4_t s = sim_tile<D>(znT, Ccols, q0, breg);
@@ -212,8 +263,14 @@ __global__ __launch_bounds__(64) void k_ntxent_fwd(const float* __restrict__ znT
       const int c = q0 + 4 * g + i;
       const float v = s[i] * inv_temp;
       const bool self = c == self_c;
-      if (rule.is_pos(my_r, c, self, i)) pos.add(v);
-      if (!self) lse_push(m, l, v);
+      if constexpr (Neg::WEIGHTED) {
+        const bool p = rule.is_pos(my_r, c, self, i);
+        if (p) pos.add(v);
+        if (!(self | p)) neg.push(m, l, v);
+      } else {
+        if (rule.is_pos(my_r, c, self, i)) pos.add(v);
+        if (!self) lse_push(m, l, v);
+      }
     }
   }
   // merge across the 4 lane groups (g) holding the same row
@@ -221,13 +278,58 @@ __global__ __launch_bounds__(64) void k_ntxent_fwd(const float* __restrict__ znT
   for (int off = 16; off < 64; off <<= 1) {
     lse_merge_lanes(m, l, off);
     pos.merge_lanes(off);
+    if constexpr (Neg::WEIGHTED) neg.merge_lanes(off);
   }
   if (g == 0) {
-    float* dst = part + ((size_t)split * R + my_r) * Rule::Pos::NP;
+    float* dst = part + ((size_t)split * R + my_r) * (Rule::Pos::NP + Neg::NX);
     dst[0] = m;
     dst[1] = l;
     pos.store(dst + 2);
+    if constexpr (Neg::WEIGHTED) neg.store(dst + Rule::Pos::NP);
   }
+}
+
+// The weighted rule's finish: merge splits in order, then per row, with N = the number of
+// negatives, u = L1 − L0, c = max(u, s_ip) (every exp argument below is <= 0):
+//   raw = N·(e^{u−c} − τ⁺·e^{s_ip−c}) / (1 − τ⁺),  floor = N·e^{−1/τ−c},  k = [raw >= floor],
+//   T = κ·e^{s_ip−c} + max(raw, floor),  loss = −s_ip + c + log T,
+//   A = k·N/(1−τ⁺)·e^{u−c}/T,  B = −1 + (κ − k·τ⁺·N/(1−τ⁺))·e^{s_ip−c}/T.
+// stats[r] = (L1, A, B, L0) for the backward passes.
+template <bool HARD>
+__global__ void k_ntxent_finish_weighted(const float* __restrict__ part, int R, int splits,
+                                         float nneg, float inv_temp, float tau_plus, float kappa,
+                                         float4* __restrict__ stats, float* __restrict__ loss) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  constexpr int NP = PairPos::NP + WeightedNeg<HARD>::NX;
+  float m = -INFINITY, l = 0.f, m0 = -INFINITY, l0 = 0.f;
+  PairPos pos;
+  for (int s = 0; s < splits; ++s) {
+    const float* p = part + ((size_t)s * R + r) * NP;
+    lse_merge_split(m, l, p);
+    pos.merge_split(p + 2);
+    if (HARD) lse_merge_split(m0, l0, p + PairPos::NP);
+  }
+  const float L1 = m + logf(l);
+  const float L0 = HARD ? m0 + logf(l0) : logf(nneg);
+  const float sp = pos.s;
+  const float u = L1 - L0;
+  const float c = fmaxf(u, sp);
+  const float eu = expf(u - c), ep = expf(sp - c);
+  const float q = nneg / (1.f - tau_plus);
+  const float raw = q * (eu - tau_plus * ep);
+  const float floor_ = nneg * expf(-inv_temp - c);
+  const bool k = raw >= floor_;
+  const float T = kappa * ep + fmaxf(raw, floor_);
+  // a clamped row has c = s_ip; decoupled (T = floor) its floor can underflow at a small
+  // temperature, where log T = log N − 1/τ − c is known and A = 0, B = −1 exactly
+  const float log_T = (!k && kappa == 0.f) ? logf(nneg) - inv_temp - c : logf(T);
+  loss[r] = -sp + c + log_T;
+  // B in the contract's form, the one the twin's autograd takes (a clamped row with κ = 1 has
+  // B = −floor/T of the order of its loss, by cancellation in fp32 on both sides)
+  const float cb = kappa - (k ? tau_plus * q : 0.f);
+  const float B = (cb != 0.f && T > 0.f) ? -1.f + cb * ep / T : -1.f;
+  stats[r] = make_float4(L1, (k && T > 0.f) ? q * eu / T : 0.f, B, L0);
 }
 
 // merge splits in order -> lse[r], loss[r] (and the label rule's inv_cnt[r] = 1/|P(r)|)
@@ -252,8 +354,10 @@ __global__ void k_ntxent_finish(const float* __restrict__ part, int R, int split
 // Backward (owned/partner). ROW mode: owned = local anchor rows (lse by owned), partners =
 // columns. COL mode: owned = columns [o0..), partners = local anchor rows (lse by partner).
 // out[split][owned][D] += Σ_q w(q,o) ẑ_q ;
-// w = gscale·(exp(s−lse_anchor) − [col∈P(anchor)]·pos_weight(anchor)); ycol covers every column
-template <bool ROW, int D, class Rule>
+// w = gscale·(exp(s−lse_anchor) − [col∈P(anchor)]·pos_weight(anchor)); ycol covers every column.
+// Weighted rule: lse holds the finish kernel's stats, (L1, A, B, L0) per local row, and
+// w = gscale·(B_anchor at the positive, A_anchor·neg_weight at a negative, 0 at the anchor's own).
+template <bool ROW, int D, class Rule, class Neg = PlainNeg, class... NegArgs>
 __global__ __launch_bounds__(64) void k_ntxent_bwd(const float* __restrict__ zn,
                                                      const float* __restrict__ znT,
                                                      const float* __restrict__ lse, int R,
@@ -263,7 +367,8 @@ __global__ __launch_bounds__(64) void k_ntxent_bwd(const float* __restrict__ zn,
                                                      int partners_per_split,
                                                      float* __restrict__ out,
                                                      const float* __restrict__ inv_cnt,
-                                                     const int* __restrict__ ycol) {
+                                                     const int* __restrict__ ycol,
+                                                     NegArgs... neg_args) {
   const int lane = threadIdx.x;
   const int g = lane >> 4, li = lane & 15;
   const int o0 = blockIdx.x * 16;  // ROW: local row index; COL: column index
@@ -280,10 +385,17 @@ __global__ __launch_bounds__(64) void k_ntxent_bwd(const float* __restrict__ zn,
 #pragma unroll
   for (int ks = 0; ks < D / 4; ++ks) breg[ks] = znT[(size_t)(4 * ks + g) * Ccols + own_col];
   Rule rule(ycol, 0, inv_cnt, n_local, col_offset, own_col);
+  [[maybe_unused]] const Neg neg{neg_args...};
+  [[maybe_unused]] const float4* __restrict__ const stats = reinterpret_cast<const float4*>(lse);
   float lse_own = 0.f, pw_own = 0.f;
+  [[maybe_unused]] float4 st_own = {0.f, 0.f, 0.f, 0.f};
   if (ROW) {
-    lse_own = lse[o0 + li];
-    pw_own = rule.pos_weight(o0 + li);
+    if constexpr (Neg::WEIGHTED) {
+      st_own = stats[o0 + li];
+    } else {
+      lse_own = lse[o0 + li];
+      pw_own = rule.pos_weight(o0 + li);
+    }
   }
   constexpr int nd = D / 16;
   f32x4_t acc[nd];
@@ -299,11 +411,19 @@ __global__ __launch_bounds__(64) void k_ntxent_bwd(const float* __restrict__ zn,
       const float v = s[i] * inv_temp;
       const int r = ROW ? o0 + li : q0 + 4 * g + i;  // anchor (local row)
       const int c = ROW ? q0 + 4 * g + i : o0 + li;  // column
-      const float la = ROW ? lse_own : lse[r];
-      const bool self = c == col_offset + r;
-      const bool pos = rule.is_pos(r, c, self, i);
-      const float p = self ? 0.f : __expf(v - la);
-      w[i] = gs * (p - (pos ? (ROW ? pw_own : rule.pos_weight(r)) : 0.f));
+      if constexpr (Neg::WEIGHTED) {
+        const float4 sa = ROW ? st_own : stats[r];  // (loaded unconditionally, as lse below)
+        const bool self = c == col_offset + r;
+        const bool pos = rule.is_pos(r, c, self, i);
+        const float p = sa.y * neg.neg_weight(v, sa);
+        w[i] = gs * (self ? 0.f : (pos ? sa.z : p));
+      } else {
+        const float la = ROW ? lse_own : lse[r];
+        const bool self = c == col_offset + r;
+        const bool pos = rule.is_pos(r, c, self, i);
+        const float p = self ? 0.f : __expf(v - la);
+        w[i] = gs * (p - (pos ? (ROW ? pw_own : rule.pos_weight(r)) : 0.f));
+      }
     }
     // acc[o][d] += Σ_q w(q,o) Z[q][d]: A[o=li][k=g] = w[t] (q = 4g+t), B[k=g][d=li] = Z[q][d]
 #pragma unroll
@@ -446,6 +566,14 @@ static void forward_range(const float* znT, const int* ycol, int y0, int R, int 
   HIP_CHECK_LAUNCH();
 }
 
+// out[i] = Σ_k part[k][i], i < n
+static void sum_splits(const float* part, int splits, size_t n, float* out, hipStream_t s) {
+  int blocks = (int)((n + 255) / 256);
+  if (blocks > 4096) blocks = 4096;
+  hipLaunchKernelGGL(k_sum_splits, dim3(blocks), dim3(256), 0, s, part, splits, n, out);
+  HIP_CHECK_LAUNCH();
+}
+
 static void backward_part(int row_mode, const float* zn, const float* znT, const float* lse,
                           const float* inv_cnt, const int* ycol, int R, int Ccols, int D,
                           int col_offset, int n_local, float inv_temp, float gscale,
@@ -462,11 +590,7 @@ static void backward_part(int row_mode, const float* zn, const float* znT, const
                                         else BWD_LAUNCH(false)));
 #undef BWD_LAUNCH
   HIP_CHECK_LAUNCH();
-  const size_t n = (size_t)nown * D;
-  int blocks = (int)((n + 255) / 256);
-  if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(k_sum_splits, dim3(blocks), dim3(256), 0, s, part, splits, n, out);
-  HIP_CHECK_LAUNCH();
+  sum_splits(part, splits, (size_t)nown * D, out, s);
 }
 
 void ntxent_forward_range(const float* znT, int R, int Ccols, int D, int col_offset, int n_local,
@@ -496,6 +620,59 @@ void ntxent_backward_part(int row_mode, const float* zn, const float* znT, const
                           hipStream_t s) {
   backward_part(row_mode, zn, znT, lse, nullptr, nullptr, R, Ccols, D, col_offset, n_local,
                 inv_temp, gscale, gout, part, splits, out, s);
+}
+
+// ---- weighted negatives (pair rule; hard-negative / debiased / decoupled NT-Xent): beta > 0
+// picks WeightedNeg<true> and its 5-float partials, beta == 0 WeightedNeg<false> (3 floats)
+void ntxent_weighted_forward_range(const float* znT, int R, int Ccols, int D, int col_offset,
+                                   int n_local, float inv_temp, float beta, float* part, int c_lo,
+                                   int c_hi, int splits, int split_base, hipStream_t s) {
+  const int ptiles = (c_hi - c_lo) / 16;
+  const int per = ((ptiles + splits - 1) / splits) * 16;
+#define WFWD_LAUNCH(HARD, ...)                                                                   \
+  hipLaunchKernelGGL((k_ntxent_fwd<DD, PairRule, WeightedNeg<HARD>>), dim3(R / 16, splits),     \
+                     dim3(64), 0, s, znT, R, Ccols, col_offset, n_local, inv_temp, per, part,    \
+                     c_lo, c_hi, split_base, (const int*)nullptr, 0, ##__VA_ARGS__)
+  DISPATCH_D(D, "ntxent", if (beta > 0.f) WFWD_LAUNCH(true, beta); else WFWD_LAUNCH(false));
+#undef WFWD_LAUNCH
+  HIP_CHECK_LAUNCH();
+}
+
+void ntxent_weighted_finish(const float* part, int R, int splits, int Ccols, float inv_temp,
+                            float beta, float tau_plus, int decoupled, float* stats, float* loss,
+                            hipStream_t s) {
+  const float nneg = (float)(Ccols - 2), kappa = decoupled ? 0.f : 1.f;
+  const dim3 grid((R + 255) / 256), block(256);
+  if (beta > 0.f)
+    hipLaunchKernelGGL(k_ntxent_finish_weighted<true>, grid, block, 0, s, part, R, splits, nneg,
+                       inv_temp, tau_plus, kappa, (float4*)stats, loss);
+  else
+    hipLaunchKernelGGL(k_ntxent_finish_weighted<false>, grid, block, 0, s, part, R, splits, nneg,
+                       inv_temp, tau_plus, kappa, (float4*)stats, loss);
+  HIP_CHECK_LAUNCH();
+}
+
+void ntxent_weighted_backward_part(int row_mode, const float* zn, const float* znT,
+                                   const float* stats, int R, int Ccols, int D, int col_offset,
+                                   int n_local, float inv_temp, float beta, float gscale,
+                                   const float* gout, float* part, int splits, float* out,
+                                   hipStream_t s) {
+  const int nown = row_mode ? R : Ccols;
+  const int npart = row_mode ? Ccols : R;
+  const int ptiles = npart / 16;
+  const int per = ((ptiles + splits - 1) / splits) * 16;
+#define WBWD_LAUNCH(ROW, HARD, ...)                                                              \
+  hipLaunchKernelGGL((k_ntxent_bwd<ROW, DD, PairRule, WeightedNeg<HARD>>),                      \
+                     dim3(nown / 16, splits), dim3(64), 0, s, zn, znT, stats, R, Ccols,          \
+                     col_offset, n_local, inv_temp, gscale, gout, per, part,                     \
+                     (const float*)nullptr, (const int*)nullptr, ##__VA_ARGS__)
+  DISPATCH_D(D, "ntxent",
+             if (beta > 0.f) { if (row_mode) WBWD_LAUNCH(true, true, beta);
+                               else WBWD_LAUNCH(false, true, beta); }
+             else { if (row_mode) WBWD_LAUNCH(true, false); else WBWD_LAUNCH(false, false); });
+#undef WBWD_LAUNCH
+  HIP_CHECK_LAUNCH();
+  sum_splits(part, splits, (size_t)nown * D, out, s);
 }
 
 // ---- label mode (SupCon): ycol must not be null (the pair rule needs n_local, which these

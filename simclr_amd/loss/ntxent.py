@@ -38,9 +38,38 @@ Extension: the supervised contrastive loss ("SupCon", Khosla et al., L_out^sup w
 * Bitwise repeatable: no atomics, a fixed merge order across lane groups and splits.
 * ``gather="ring"`` with ``supervised`` is a ``ValueError``; limits as NT-Xent (R % 16 == 0,
   D in {32, 64, 128, 256} for the HIP path).
+
+Extension: weighted negatives, ``NTXent(..., hard_beta=β, tau_plus=τ⁺, decoupled=bool)``
+(``loss.hard_beta``, ``loss.tau_plus``, ``loss.decoupled``): hard-negative sampling (Robinson et
+al. 2021, negatives importance-weighted by exp(β·s)), the debiased loss (Chuang et al. 2020, the
+expected share τ⁺ of false negatives subtracted) and decoupled contrastive learning (Yeh et al.
+2022, the positive leaves the denominator).  The loss is "weighted" when any of the three
+differs from its default (0, 0, False); otherwise it is NT-Xent, by the same ops in the same
+order.  The contract, identical on the GPU and in :func:`nt_xent_weighted_torch`:
+
+* Rows, columns (local or all-gathered), ẑ, ``s``, ``col_offset``, the own column and the
+  positive p(i) are NT-Xent's.  Neg(i) = every column but i's own and its positive,
+  N = Ccols − 2.
+* ``L1_i = LSE_{a∈Neg(i)} (1+β)·s_ia``, ``L0_i = LSE_{a∈Neg(i)} β·s_ia`` (β = 0: L0 = log N
+  exactly, no second sum), ``u_i = L1_i − L0_i``.
+* With ``c_i = max(u_i, s_ip)``: ``raw_i = N·(exp(u_i − c_i) − τ⁺·exp(s_ip − c_i)) / (1 − τ⁺)``,
+  ``floor_i = N·exp(−1/τ − c_i)`` (the published clamp at N·e^{−1/τ}),
+  ``Ng_i = max(raw_i, floor_i)``, ``T_i = κ·exp(s_ip − c_i) + Ng_i`` with κ = 0 if decoupled,
+  else 1; ``loss_i = −s_ip + c_i + log T_i``.  Every exp argument is <= 0.
+* ``mean`` = Σ_i loss_i / R, ``sum`` the plain sum, ``none`` (2, n) on the torch path only.
+* Gradient in normalised space, ``k_i = [raw_i >= floor_i]``:
+  ``A_i = k_i·N/(1−τ⁺)·exp(u_i − c_i)/T_i``,
+  ``B_i = −1 + (κ − k_i·τ⁺·N/(1−τ⁺))·exp(s_ip − c_i)/T_i``,
+  ``dS_ia = g·A_i·((1+β)·exp((1+β)s_ia − L1_i) − β·exp(β·s_ia − L0_i))`` for a ∈ Neg(i),
+  ``dS_ip = g·B_i``, ``dS_ii = 0``; a clamped row (k = 0) has no gradient through its
+  negatives, as published.
+* Bitwise repeatable, the plain kernels' merge order; ``gather=True`` is supported,
+  ``gather="ring"``, ``supervised`` and the other ``loss.kind`` values are not (``ValueError``);
+  limits as NT-Xent, anything else and ``reduction="none"`` take the twin.
 """
 from __future__ import annotations
 
+import math
 from typing import Optional
 
 import torch
@@ -76,6 +105,80 @@ def nt_xent_torch(z: torch.Tensor, n: int, temperature: float, reduction: str = 
     if reduction == "sum":
         return rows.sum()
     return rows.sum() / n * 0.5
+
+
+def check_negatives(hard_beta, tau_plus, decoupled) -> bool:
+    """The three weighted-negatives arguments; returns whether the loss is "weighted" (any of
+    them differs from its default).  ``ValueError`` names the failing key."""
+    for key, v in (("loss.hard_beta", hard_beta), ("loss.tau_plus", tau_plus)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)):
+            raise ValueError(f"{key} must be a number, got {v!r}")
+        if not math.isfinite(v):
+            raise ValueError(f"{key} must be finite, got {v!r}")
+    if hard_beta < 0:
+        raise ValueError(f"loss.hard_beta must be >= 0, got {hard_beta!r}")
+    if not 0 <= tau_plus < 1:
+        raise ValueError(f"loss.tau_plus must be in [0, 1), got {tau_plus!r}")
+    if not isinstance(decoupled, bool):
+        raise ValueError(f"loss.decoupled must be a boolean, got {decoupled!r}")
+    return hard_beta > 0 or tau_plus > 0 or decoupled
+
+
+def nt_xent_weighted_torch(z: torch.Tensor, n: int, temperature: float, hard_beta: float,
+                           tau_plus: float, decoupled: bool, reduction: str = "mean",
+                           gather: bool = False, group=None, world_size: int = 1, rank: int = 0):
+    """NT-Xent with weighted negatives on torch ops (the contract in the module docstring);
+    ``z`` = [view0; view1] of shape [2n, d].  All three arguments at their defaults: NT-Xent
+    itself, :func:`nt_xent_torch`."""
+    if not check_negatives(hard_beta, tau_plus, decoupled):
+        return nt_xent_torch(z, n, temperature, reduction, gather, group, world_size, rank)
+    zn = F.normalize(z if z.dtype == torch.float64 else z.float(), p=2, dim=1)
+    R = zn.shape[0]
+    if gather and world_size > 1:
+        from torch.distributed.nn.functional import all_gather
+        cols = torch.cat(all_gather(zn, group=group), dim=0)
+        col_offset = rank * R
+    else:
+        cols = zn
+        col_offset = 0
+    sim = zn @ cols.t() / temperature
+    rows = weighted_rows(sim, n, col_offset, temperature, hard_beta, tau_plus, decoupled)
+    if reduction == "none":
+        return rows.view(2, n)
+    if reduction == "sum":
+        return rows.sum()
+    return rows.sum() / n * 0.5
+
+
+def weighted_rows(sim: torch.Tensor, n: int, col_offset: int, temperature: float,
+                  hard_beta: float, tau_plus: float, decoupled: bool) -> torch.Tensor:
+    """loss_i of the weighted-negatives contract from the similarities ``sim`` [2n][Ccols]
+    (= s, already divided by τ); row i's own column is ``col_offset + i``."""
+    R = sim.shape[0]
+    idx = torch.arange(R, device=sim.device)
+    pcol = col_offset + torch.where(idx < n, idx + n, idx - n)
+    s_p = sim[idx, pcol]
+    out = torch.zeros_like(sim, dtype=torch.bool)  # not in Neg(i): the own column, the positive
+    out[idx, col_offset + idx] = True
+    out[idx, pcol] = True
+    neg = sim.masked_fill(out, float("-inf"))
+    N = sim.shape[1] - 2
+    L1 = torch.logsumexp((1.0 + hard_beta) * neg, dim=1)
+    u = L1 - (torch.logsumexp(hard_beta * neg, dim=1) if hard_beta > 0 else math.log(N))
+    # the loss does not depend on the shift c (the floor moves with it), so c carries no gradient
+    c = torch.maximum(u, s_p).detach()
+    e_p = torch.exp(s_p - c)
+    raw = N * (torch.exp(u - c) - tau_plus * e_p) / (1.0 - tau_plus)
+    floor = N * torch.exp(-1.0 / temperature - c)
+    if decoupled:
+        # log max(raw, floor): a clamped row has c = s_ip, and at a small temperature its floor
+        # N·exp(−1/τ − c) underflows fp32 while its logarithm is known
+        k = raw >= floor
+        log_T = torch.where(k, torch.log(torch.where(k, raw, torch.ones_like(raw))),
+                            math.log(N) - 1.0 / temperature - c)
+    else:
+        log_T = torch.log(e_p + torch.maximum(raw, floor))
+    return -s_p + c + log_T
 
 
 def _check_labels(labels, n: int, device) -> torch.Tensor:
@@ -159,10 +262,14 @@ class _NTXentHipFn(torch.autograd.Function):
     (``nt_sup_*``): the rank's view-expanded int32 label block is built on the device
     (``nt_expand_labels``) and, for the gathered loss, all-gathered on the side stream right
     behind z.  The order of the ``torch.empty`` calls, launches, collectives and stream waits
-    of each mode is part of the contract: the step is captured into a graph and replayed."""
+    of each mode is part of the contract: the step is captured into a graph and replayed.
+
+    ``neg`` = (β, τ⁺, decoupled) selects the weighted-negatives kernels (``nt_w_*``, ``y`` None):
+    the row buffer ``lse`` then holds (L1, A, B, L0) per row and the forward partials 5 floats
+    per row if β > 0; everything else, the order included, is the plain mode's."""
 
     @staticmethod
-    def forward(ctx, z, y, n, temperature, reduction, gather, st):
+    def forward(ctx, z, y, n, temperature, reduction, gather, st, neg=None):
         from ..ops import _ext
         ops = _ext.ops()
         R, D = z.shape
@@ -171,7 +278,10 @@ class _NTXentHipFn(torch.autograd.Function):
         inv_t = 1.0 / temperature
         labelled = y is not None
         npart = 4 if labelled else 3  # floats per row of a forward partial
-        lse = torch.empty((R,), device=dev, dtype=torch.float32)
+        if neg is not None:
+            beta, tau_plus, decoupled = neg
+            npart = 5 if beta > 0 else 3
+        lse = torch.empty((R, 4) if neg is not None else (R,), device=dev, dtype=torch.float32)
         inv_cnt = torch.empty((R,), device=dev, dtype=torch.float32) if labelled else None
         rows = torch.empty((R,), device=dev, dtype=torch.float32)
         y_loc = ycol = None
@@ -184,12 +294,18 @@ class _NTXentHipFn(torch.autograd.Function):
             if labelled:
                 ops.nt_sup_forward_range(znT, labels, y0, R, col_offset, n, inv_t, part, lo, hi,
                                          splits, base)
+            elif neg is not None:
+                ops.nt_w_forward_range(znT, R, col_offset, n, inv_t, beta, part, lo, hi, splits,
+                                       base)
             else:
                 ops.nt_forward_range(znT, R, col_offset, n, inv_t, part, lo, hi, splits, base)
 
         def finish(splits):
             if labelled:
                 ops.nt_sup_finish(part, R, splits, lse, inv_cnt, rows)
+            elif neg is not None:
+                ops.nt_w_finish(part, R, splits, Ccols, inv_t, beta, tau_plus, decoupled, lse,
+                                rows)
             else:
                 ops.nt_finish(part, R, splits, lse, rows)
 
@@ -274,7 +390,7 @@ class _NTXentHipFn(torch.autograd.Function):
         scale = 1.0 / R if reduction == "mean" else 1.0
         ops.nt_reduce_loss(rows, scale, out)
         ctx.save_for_backward(zn, zall, znT, lse, inv, inv_cnt, ycol)
-        ctx.cfg = (n, inv_t, scale, col_offset, gather, st, z.dtype)
+        ctx.cfg = (n, inv_t, scale, col_offset, gather, st, z.dtype, neg)
         return out.view(())
 
     @staticmethod
@@ -282,7 +398,7 @@ class _NTXentHipFn(torch.autograd.Function):
         from ..ops import _ext
         ops = _ext.ops()
         zn, zall, znT, lse, inv, inv_cnt, ycol = ctx.saved_tensors
-        n, inv_t, scale, col_offset, gather, st, zdtype = ctx.cfg
+        n, inv_t, scale, col_offset, gather, st, zdtype, neg = ctx.cfg
         R, D = zn.shape
         Ccols = zall.shape[0]
         dev = zn.device
@@ -292,6 +408,9 @@ class _NTXentHipFn(torch.autograd.Function):
             if ycol is not None:
                 ops.nt_sup_backward_part(row_mode, zall, znT, lse, inv_cnt, ycol, R, col_offset,
                                          n, inv_t, scale, g, part, splits, out)
+            elif neg is not None:
+                ops.nt_w_backward_part(row_mode, zall, znT, lse, R, col_offset, n, inv_t, neg[0],
+                                       scale, g, part, splits, out)
             else:
                 ops.nt_backward_part(row_mode, zall, znT, lse, R, col_offset, n, inv_t, scale, g,
                                      part, splits, out)
@@ -332,16 +451,18 @@ class _NTXentHipFn(torch.autograd.Function):
         else:
             dz = torch.empty((R, D), device=dev, dtype=torch.float32)
             ops.nt_normalize_backward(zn, inv, d_rows, None, dz)
-        return dz, None, None, None, None, None, None
+        return dz, None, None, None, None, None, None, None
 
 
 class NTXent(nn.Module):
     def __init__(self, temperature: float = 0.1, reduction: str = "mean",
-                 device: Optional[torch.device] = None, gather=False, supervised: bool = False):
+                 device: Optional[torch.device] = None, gather=False, supervised: bool = False,
+                 hard_beta: float = 0.0, tau_plus: float = 0.0, decoupled: bool = False):
         """``gather``: False (reference, per-GPU negatives), True (all-gathered global
         negatives, fused kernel) or ``"ring"`` (global negatives circulated around the ranks,
         loss/ring.py).  ``supervised``: the SupCon loss (module docstring); ``forward`` then
-        needs ``labels``."""
+        needs ``labels``.  ``hard_beta`` >= 0, ``tau_plus`` in [0, 1), ``decoupled``: weighted
+        negatives (module docstring); not with ``supervised`` or the ring."""
         assert temperature > 0.0
         assert reduction in {"none", "mean", "sum"}
         super().__init__()
@@ -352,6 +473,17 @@ class NTXent(nn.Module):
         if self.supervised and self.gather == "ring":
             raise ValueError("loss.supervised=true is not available with loss.gather=ring "
                              "(use loss.gather=true for global columns)")
+        self.weighted = check_negatives(hard_beta, tau_plus, decoupled)
+        self.hard_beta, self.tau_plus, self.decoupled = float(hard_beta), float(tau_plus), decoupled
+        if self.weighted:
+            keys = "loss.hard_beta / loss.tau_plus / loss.decoupled"
+            if self.supervised:
+                raise ValueError(f"{keys} are not available with loss.supervised=true")
+            if self.gather == "ring":
+                raise ValueError(f"{keys} are not available with loss.gather=ring "
+                                 "(use loss.gather=true for global columns)")
+        # (β, τ⁺, decoupled) of the weighted kernels; None: plain NT-Xent / SupCon
+        self._neg = (self.hard_beta, self.tau_plus, self.decoupled) if self.weighted else None
 
     def forward(self, view0: torch.Tensor, view1: Optional[torch.Tensor] = None,
                 labels: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -379,7 +511,12 @@ class NTXent(nn.Module):
             return nt_xent_ring(z, n, self.temperature, st.group, st.world_size, st.rank)
         if (z.is_cuda and self.reduction != "none" and registry.use_hip(z) and R % 16 == 0
                 and D in (32, 64, 128, 256)):
-            return _NTXentHipFn.apply(z, y, n, self.temperature, self.reduction, self.gather, st)
+            return _NTXentHipFn.apply(z, y, n, self.temperature, self.reduction, self.gather, st,
+                                      self._neg)
+        if self.weighted:
+            return nt_xent_weighted_torch(z, n, self.temperature, self.hard_beta, self.tau_plus,
+                                          self.decoupled, self.reduction, self.gather, st.group,
+                                          st.world_size, st.rank)
         if self.supervised:
             return sup_con_torch(z, n, y, self.temperature, self.reduction, self.gather,
                                  st.group, st.world_size, st.rank)

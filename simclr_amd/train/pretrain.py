@@ -38,7 +38,7 @@ from ..data.datasets import load_dataset
 from ..data.loader import ContrastiveLoader, blur_kernel_from_cfg
 from ..loss.barlow import BarlowTwins
 from ..loss.nnclr import NNCLR
-from ..loss.ntxent import NTXent
+from ..loss.ntxent import NTXent, check_negatives
 from ..models.contrastive import ContrastiveModel
 from ..ops import registry
 from ..optim.lars import FusedLARS, weight_decay_per_param
@@ -100,6 +100,12 @@ class Trainer:
         # loss.kind: ntxent (default), barlow (Barlow Twins, loss/barlow.py: per rank, no labels)
         # or nnclr (loss/nnclr.py: per rank, no labels, a support set of past embeddings)
         kind = cfg_get(cfg, "loss.kind", None) or "ntxent"
+        # loss.hard_beta / loss.tau_plus / loss.decoupled: weighted negatives, NT-Xent only
+        if kind != "ntxent" and check_negatives(cfg_get(cfg, "loss.hard_beta", 0.0),
+                                                cfg_get(cfg, "loss.tau_plus", 0.0),
+                                                cfg_get(cfg, "loss.decoupled", False)):
+            raise ValueError("loss.hard_beta / loss.tau_plus / loss.decoupled are not available "
+                             f"with loss.kind={kind}")
         if kind == "barlow":
             if self.supervised or cfg_get(cfg, "loss.gather", False) not in (None, False):
                 raise ValueError("loss.kind=barlow is not available with loss.supervised or "
@@ -111,7 +117,10 @@ class Trainer:
         elif kind == "ntxent":
             self.loss_fn = NTXent(temperature=cfg["parameter"]["temperature"],
                                   gather=cfg_get(cfg, "loss.gather", False),
-                                  supervised=self.supervised)
+                                  supervised=self.supervised,
+                                  hard_beta=cfg_get(cfg, "loss.hard_beta", 0.0),
+                                  tau_plus=cfg_get(cfg, "loss.tau_plus", 0.0),
+                                  decoupled=cfg_get(cfg, "loss.decoupled", False))
         elif kind == "nnclr":
             # NNCLR (loss/nnclr.py): the support set and its cursor are built here, after the
             # model, from a generator of their own, so no other initialisation depends on them

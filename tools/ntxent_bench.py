@@ -123,6 +123,68 @@ def main_supervised(classes, widths, rounds, reps):
             print(" ".join(line) + f" splits {splits}/{s_col}/{s_row}", flush=True)
 
 
+def main_negatives(widths, rounds, reps):
+    """``--negatives``: the weighted-negatives kernels (``HARD`` off: β = 0, τ⁺ = 0.1; ``HARD``
+    on: β = 1, τ⁺ = 0.1) against the plain NT-Xent ones on the same ẑ, the three alternating
+    round by round in one process: forward (+finish/reduce), column pass, row pass; medians over
+    the rounds, median and min-max of the per-round ratio to the plain loss."""
+    from simclr_amd.ops import _ext
+    ops = _ext.ops()
+    dev = torch.device("cuda", 0)
+    R, D, n = 1024, 128, 512
+    inv_t, tau_plus = 2.0, 0.1
+    for W in widths:
+        C = W * R
+        zall = torch.nn.functional.normalize(torch.randn(C, D, device=dev), dim=1)
+        znT = torch.empty(D, C, device=dev)
+        ops.nt_transpose(zall, znT)
+        splits = ops.nt_fwd_splits(R, C)
+        s_col, s_row = ops.nt_bwd_splits(C, R), ops.nt_bwd_splits(R, C)
+        part = torch.empty(splits * R * 5, device=dev)
+        lse, rows = torch.empty(R, device=dev), torch.empty(R, device=dev)
+        stats = {b: torch.empty(R, 4, device=dev) for b in (0.0, 1.0)}
+        out, g = torch.empty(1, device=dev), torch.ones(1, device=dev)
+        p2, dc = torch.empty(s_col * C * D, device=dev), torch.empty(C, D, device=dev)
+        p1, dr = torch.empty(s_row * R * D, device=dev), torch.empty(R, D, device=dev)
+
+        def fwd_nt():
+            ops.nt_forward(znT, R, 0, n, inv_t, part, splits, lse, rows)
+            ops.nt_reduce_loss(rows, 1.0 / R, out)
+
+        def fwd_w(beta):
+            ops.nt_w_forward_range(znT, R, 0, n, inv_t, beta, part, 0, C, splits, 0)
+            ops.nt_w_finish(part, R, splits, C, inv_t, beta, tau_plus, False, stats[beta], rows)
+            ops.nt_reduce_loss(rows, 1.0 / R, out)
+
+        def bwd_w(row_mode, beta):
+            ws, sp, dst = (p1, s_row, dr) if row_mode else (p2, s_col, dc)
+            ops.nt_w_backward_part(row_mode, zall, znT, stats[beta], R, 0, n, inv_t, beta,
+                                   1.0 / R, g, ws, sp, dst)
+        arms = {
+            "fwd": (fwd_nt, lambda: fwd_w(0.0), lambda: fwd_w(1.0)),
+            "bwd cols": (
+                lambda: ops.nt_backward_part(False, zall, znT, lse, R, 0, n, inv_t, 1.0 / R, g,
+                                             p2, s_col, dc),
+                lambda: bwd_w(False, 0.0), lambda: bwd_w(False, 1.0)),
+            "bwd rows": (
+                lambda: ops.nt_backward_part(True, zall, znT, lse, R, 0, n, inv_t, 1.0 / R, g,
+                                             p1, s_row, dr),
+                lambda: bwd_w(True, 0.0), lambda: bwd_w(True, 1.0)),
+        }
+        fwd_nt(), fwd_w(0.0), fwd_w(1.0)  # (lse / stats for the backward arms)
+        for name, fns in arms.items():
+            t = [[], [], []]
+            for _ in range(rounds):
+                for k, f in enumerate(fns):
+                    t[k].append(timeit(f, reps))
+            line = f"cols={C} {name}: plain {_median(t[0]):.1f} us"
+            for k, label in ((1, "weighted"), (2, "weighted hard")):
+                ratios = [b / a for a, b in zip(t[0], t[k])]
+                line += (f"; {label} {_median(t[k]):.1f} us ratio {_median(ratios):.3f} "
+                         f"[{min(ratios):.3f}, {max(ratios):.3f}]")
+            print(line + f"; splits {splits}/{s_col}/{s_row}", flush=True)
+
+
 if __name__ == "__main__":
     import argparse
     ap = argparse.ArgumentParser(description=__doc__)
@@ -131,11 +193,17 @@ if __name__ == "__main__":
     ap.add_argument("--classes", type=int, nargs="+", default=[10, 100],
                     help="--supervised: number of distinct labels (one run per value)")
     ap.add_argument("--ranks", type=int, nargs="+", default=[1, 8],
-                    help="--supervised: column counts as multiples of the 1024 local rows")
+                    help="--supervised / --negatives: column counts as multiples of the 1024 "
+                         "local rows")
+    ap.add_argument("--negatives", action="store_true",
+                    help="time the weighted-negatives kernels (HARD off and on) against the "
+                         "plain ones")
     ap.add_argument("--rounds", type=int, default=15)
     ap.add_argument("--reps", type=int, default=200)
     a = ap.parse_args()
-    if a.supervised:
+    if a.negatives:
+        main_negatives(a.ranks, a.rounds, a.reps)
+    elif a.supervised:
         main_supervised(a.classes, a.ranks, a.rounds, a.reps)
     else:
         main()
